@@ -18,7 +18,14 @@ fleet slice (``--agents`` per GPU, weak scaling, no data-path collective);
 barrier + synchronize bracket the timed steps and the max time over ranks is
 reported.
 
-Extra JSON fields: ``roofline`` for the dominant kernel (mpcx_ipm_solve; kernel time measured
+A plain run (``--gpus 1 --steps K --warmup W``) sets the C3 fleet up, runs W untimed and K
+timed steps, writes the last step's outputs if ``--dump-outputs DIR`` is given and prints the
+result line (``value``, ``ms_per_step``, the C3 ``config``).  Everything else runs only with
+``--full``: the other legs (C4 / C5 / C2 ADMM, NARX, MHE, the plugin-API end-to-end leg, C1
+latency, the fixed-fleet C3 split on several GPUs), the CPU baselines and the roofline block;
+the leg options (``--admm-agents``, ``--no-e2e``, ``--no-cpu-baseline``, ...) select among them.
+
+Extra JSON fields of ``--full``: ``roofline`` for the dominant kernel (mpcx_ipm_solve; kernel time measured
 with HIP events on the launch stream; ``roofline_block``: bound "hbm" -- the counters show the
 memory side as the limit -- with the algorithmic bytes as ``achieved``, the counted bytes as
 ``traffic`` / ``memory_side`` and the algorithmic FP64 flops beside them) and ``cpu_baseline``
@@ -50,6 +57,7 @@ METRIC = "converged MPC solves/sec (whole node) at N agents; ADMM iters/sec to c
 PEAK_FP64_TFLOPS = 78.6   # MI355X FP64 vector peak (spec)
 PEAK_HBM_GBS = 8000.0
 MEASURED_HBM_GBS = 6300.0  # MI355X_MICROARCH.md: ~6.3 TB/s achievable
+DUMP_LIMIT_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much (npy headers aside)
 
 
 def fleet_values(n, seed):
@@ -212,6 +220,31 @@ def pmc_traffic(code_object: str, n_agents: int):
         if d.get("code_object") == code_object:
             return float(d["hbm_bytes_per_launch"]), os.path.relpath(path, ROOT)
     return None, None
+
+
+def dump_outputs(directory, rank, w, lam_g, stats_bytes):
+    """``--dump-outputs``: what the last timed step handed back, as float64 ``.npy`` files:
+    ``w`` [n, nw] (the primal solutions), ``lam_g`` [n, ng] (the constraint multipliers) and
+    ``stats`` [n, 18] (one ``mpcx_stats`` record per agent, its fields in declaration order:
+    obj, primal_inf, dual_inf, compl_inf, mu, obj_scale, then the integer counters from
+    iter_count on).  The inputs are seeded, so two builds run with the same arguments can be
+    compared array for array.  Ranks past 0 write ``<name>.rank<r>.npy``.  A fleet whose
+    arrays exceed ``DUMP_LIMIT_BYTES`` is cut to a fixed seeded sample of its agents (the same
+    rows of every array, in ascending order)."""
+    from agentlib_mpc_amd.runtime.native import stats_array
+
+    os.makedirs(directory, exist_ok=True)
+    rec = stats_array(stats_bytes)
+    arrays = {"w": w.cpu().numpy(), "lam_g": lam_g.cpu().numpy(),
+              "stats": np.stack([rec[name].astype(np.float64) for name in rec.dtype.names], axis=1)}
+    n = len(rec)
+    row_bytes = 8 * sum(a.shape[1] for a in arrays.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(20261015).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+    for name, a in arrays.items():
+        suffix = f".rank{rank}" if rank else ""
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def admm_bench(args, world, rank, dev):
@@ -877,6 +910,12 @@ def main():
     ap.add_argument("--admm-steps", type=int, default=5,
                     help="closed-loop control steps of the coordinated legs (C2, C5), each to the stopping rule")
     ap.add_argument("--no-e2e", action="store_true", help="skip the plugin-API end-to-end leg and C1 latency")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline C3 steps also run every other leg (C4, C5, C2, MHE, plugin API, C1 "
+                         "latency, fixed-fleet C3 on several GPUs), the CPU baselines and the roofline block; the "
+                         "leg options above only apply with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (w, lam_g, stats) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -942,22 +981,25 @@ def main():
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
+    st_host = st.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, tw, lam, st_host)
 
-    c3s = c3_strong_bench(args, world, rank, dev) if world > 1 else None
-    admm = admm_bench(args, world, rank, dev) if args.admm_agents > 0 else None
-    nn = nn_bench(args, world, rank, dev) if args.nn_zones > 0 else None
-    c5 = c5_admm_bench(args, world, rank, dev) if args.c5_blocks > 0 else None
-    c2 = c2_admm_bench(args, world, rank, dev) if args.c2_blocks > 0 else None
-    mhe = mhe_bench(args, world, rank, dev) if args.mhe_agents > 0 else None
-    e2e = e2e_bench(args, world, rank, dev) if not args.no_e2e else None
-    c1 = c1_latency(args, dev) if not args.no_e2e and rank == 0 else None
-    stats = stats_to_dicts(st.cpu().numpy().tobytes())
+    full = args.full
+    c3s = c3_strong_bench(args, world, rank, dev) if full and world > 1 else None
+    admm = admm_bench(args, world, rank, dev) if full and args.admm_agents > 0 else None
+    nn = nn_bench(args, world, rank, dev) if full and args.nn_zones > 0 else None
+    c5 = c5_admm_bench(args, world, rank, dev) if full and args.c5_blocks > 0 else None
+    c2 = c2_admm_bench(args, world, rank, dev) if full and args.c2_blocks > 0 else None
+    mhe = mhe_bench(args, world, rank, dev) if full and args.mhe_agents > 0 else None
+    e2e = e2e_bench(args, world, rank, dev) if full and not args.no_e2e else None
+    c1 = c1_latency(args, dev) if full and not args.no_e2e and rank == 0 else None
+    stats = stats_to_dicts(st_host.tobytes())
     n_ok = sum(1 for s in stats if s["success"])
     arr = {"iter": np.array([s["iter_count"] for s in stats]),
            "fact": np.array([s["n_factorizations"] for s in stats]),
            "trials": np.array([s["n_trials"] for s in stats]),
            "dense": np.array([s["n_dense_stages"] for s in stats])}
-    flops = flops_model(prob.gen, arr)
 
     t_max = torch.tensor([wall], dtype=torch.float64, device=dev)
     ok_t = torch.tensor([float(n_ok)], dtype=torch.float64, device=dev)
@@ -968,9 +1010,6 @@ def main():
     total_ok = float(ok_t.item())
     value = total_ok * args.steps / wall
     if rank == 0:
-        from agentlib_mpc_amd.runtime.native import code_object_path
-        traffic, traffic_src = pmc_traffic(code_object_path(prob.gen.key).name, n)
-        io_bytes = n * 8 * (prob.nlp.npar + 3 * prob.nlp.nw + prob.nlp.ng_total) + n * STATS_BYTES
         out = {
             "metric": METRIC,
             "value": value,
@@ -1000,9 +1039,13 @@ def main():
                 "ipm_iterations_p50_p99_max": [float(np.percentile(arr["iter"], q)) for q in (50, 99, 100)],
                 "parallelism": f"agent-partitioned dp{world}",
             },
-            "roofline": roofline_block(kernel_ms, io_bytes, flops, traffic, traffic_src,
-                                       pmc_fp64(code_object_path(prob.gen.key).name, n, kernel_ms)),
         }
+        if full:
+            from agentlib_mpc_amd.runtime.native import code_object_path
+            traffic, traffic_src = pmc_traffic(code_object_path(prob.gen.key).name, n)
+            io_bytes = n * 8 * (prob.nlp.npar + 3 * prob.nlp.nw + prob.nlp.ng_total) + n * STATS_BYTES
+            out["roofline"] = roofline_block(kernel_ms, io_bytes, flops_model(prob.gen, arr), traffic, traffic_src,
+                                             pmc_fp64(code_object_path(prob.gen.key).name, n, kernel_ms))
         if c3s is not None:
             out["c3_strong"] = c3s
         if admm is not None:
@@ -1019,7 +1062,7 @@ def main():
             out["e2e"] = e2e
         if c1 is not None:
             out["c1_latency"] = c1
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(p, lbw, ubw, w0, oracle_opts)
             except Exception as e:  # pragma: no cover
