@@ -484,9 +484,18 @@ def exchange_supply_inputs(prob, N=10, penalty=0.1, rho=1e4, diff=None, lam=None
 # C5: three-zone NARX room, backend "casadi_admm_nn", multiple shooting
 # ---------------------------------------------------------------------------
 
+_ANN_ACTIVATIONS = {
+    "tanh": torch.tanh,
+    "softplus": lambda a: torch.log1p(torch.exp(a)),   # the reference's log(1 + exp(a))
+    "exponential": torch.exp,
+    "gaussian": lambda a: torch.exp(-a * a),
+}
+
+
 def _ann_torch(layers):
-    """Sequential forward of a BatchNormalization -> Dense(sigmoid) -> Dense(linear)
-    network given as [(kind, arrays)] (`models/casadi_predictor.py:306-376`)."""
+    """Sequential forward of a BatchNormalization -> Dense(activation) -> Dense(linear)
+    network given as [(kind, arrays)] (`models/casadi_predictor.py:306-376`; the activations
+    of `casadi_predictor.py:255-277` that have smooth derivatives, which autograd supplies)."""
     def fwd(x):
         for kind, arrs in layers:
             if kind == "bn":
@@ -496,9 +505,12 @@ def _ann_torch(layers):
             elif kind == "sigmoid":
                 W, b = arrs
                 x = torch.sigmoid(x @ torch.as_tensor(W) + torch.as_tensor(b))
-            else:
+            elif kind == "linear":
                 W, b = arrs
                 x = x @ torch.as_tensor(W) + torch.as_tensor(b)
+            else:
+                W, b = arrs
+                x = _ANN_ACTIVATIONS[kind](x @ torch.as_tensor(W) + torch.as_tensor(b))
         return x
     return fwd
 
@@ -634,7 +646,9 @@ def ann_layers_from_serialized(layer_specs):
             out.append(("bn", (w[0], w[1], w[2], w[3], float(spec["config"].get("epsilon", 1e-3)))))
         elif spec["class_name"] == "Dense":
             act = spec["config"].get("activation", "linear")
-            out.append(("sigmoid" if act == "sigmoid" else "linear", (w[0], w[1])))
+            if act != "sigmoid" and act != "linear" and act not in _ANN_ACTIVATIONS:
+                raise ValueError(f"activation {act!r} is not restated by the oracle")
+            out.append((act, (w[0], w[1])))
     return out
 
 

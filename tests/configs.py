@@ -92,6 +92,53 @@ def room_nn(**kw) -> Case:
     return Case(be, cv, prob, nlps.room_nn_inputs(prob, N=N, **o))
 
 
+#: act(0) of the hidden activations: ``b2 = -act(0) sum(W2)`` centres the one-step change
+_ACT_AT_ZERO = {"sigmoid": 0.5, "tanh": 0.0, "linear": 0.0, "softplus": float(np.log(2.0)),
+                "exponential": 1.0, "gaussian": 1.0}
+
+
+def topology_ann(features: dict, seed: int, hidden: int, activation: str, dt: float = 1800.0):
+    """``models/examples.py::synthetic_ann`` (BatchNormalization -> Dense -> Dense(1, linear) on
+    the lagged features of the three-zone example) with the given width and activation."""
+    from agentlib_mpc_amd.data_structures.ml_model_datatypes import Feature, OutputFeature, column_order
+    from agentlib_mpc_amd.models import examples as ex
+    from agentlib_mpc_amd.models.serialized_ml_model import SerializedANN
+
+    rng = np.random.default_rng(seed)
+    inputs = {n: Feature(name=n, lag=l) for n, l in features["inputs"].items()}
+    oname, olag = features["output"]
+    outputs = {oname: OutputFeature(name=oname, lag=olag, output_type="difference", recursive=True)}
+    cols = column_order(inputs, outputs)
+    base = [c.rsplit("_", 1)[0] if c not in ex._FEATURE_SCALE else c for c in cols]
+    mean = np.array([ex._FEATURE_SCALE[b][0] for b in base])
+    var = np.array([ex._FEATURE_SCALE[b][1] ** 2 for b in base])
+    n_in = len(cols)
+    W1 = rng.normal(0.0, 1.0 / np.sqrt(n_in), (n_in, hidden))
+    b1 = rng.normal(0.0, 0.1, hidden)
+    W2 = rng.normal(0.0, 0.6 / np.sqrt(hidden), (hidden, 1))
+    b2 = np.array([-_ACT_AT_ZERO[activation] * W2[:, 0].sum()])
+    layers = [
+        {"class_name": "BatchNormalization", "config": {"axis": -1, "epsilon": 0.001},
+         "weights": [np.ones(n_in), np.zeros(n_in), mean, var]},
+        {"class_name": "Dense", "config": {"units": hidden, "activation": activation}, "weights": [W1, b1]},
+        {"class_name": "Dense", "config": {"units": 1, "activation": "linear"}, "weights": [W2, b2]},
+    ]
+    return SerializedANN.from_layers(layers, dt=dt, input=inputs, output=outputs)
+
+
+def room_nn_topology(hidden, activation, N=8, seed=7, **kw) -> Case:
+    """``room_nn`` with two seeded networks of ``hidden`` units and the given activation."""
+    from agentlib_mpc_amd.models import examples as ex
+
+    anns = [topology_ann(ex.T_AIR_FEATURES, seed, hidden, activation),
+            topology_ann(ex.T_CCA_FEATURES, seed + 1, hidden, activation)]
+    be, cv = bm.room_nn(anns=anns, N=N, **kw)
+    air, cca = (nlps.ann_layers_from_serialized(a.layer_specs()) for a in anns)
+    assert air[1][0] == cca[1][0] == activation
+    prob = nlps.room_nn(air, cca, N=N)
+    return Case(be, cv, prob, nlps.room_nn_inputs(prob, N=N, **kw))
+
+
 def _tz(kind, **kw) -> Case:
     be, cv = (bm.tz_ahu if kind == "ahu" else bm.tz_cca)(**kw)
     N = kw.get("N", 24)

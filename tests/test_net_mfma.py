@@ -1,6 +1,7 @@
 """The NARX networks are evaluated on the FP64 matrix cores (CPU checks of the generated
-code; the numerics are checked on the GPU by the room_nn / C5 parity cases in
-tests/test_gpu_ipm.py and tests/test_gpu_admm.py).
+code; the numerics are checked on the GPU by tests/test_net_eval.py, which runs
+``mpcx_net::eval`` alone, and by the room_nn / C5 parity cases in tests/test_gpu_ipm.py,
+tests/test_gpu_net_topologies.py and tests/test_gpu_admm.py).
 
 Reference: the serialized ANN evaluated by CasADi inside IPOPT
 (`agentlib_mpc/models/casadi_predictor.py:306-336`); here one batched
@@ -53,6 +54,33 @@ def test_second_derivative_tables_are_pair_products():
                    for r in rows)
 
     assert any(pair_products(sx.network(i).W1) for i in range(len(sx._NETWORKS)))
+
+
+def test_network_section_follows_the_topology():
+    """A 20-unit tanh pair of networks (tests/configs.py::room_nn_topology): the template
+    arguments carry the width and the activation code, the derivative tables stay sorted."""
+    from tests import configs
+
+    src = configs.room_nn_topology(20, "tanh", N=8).backend.problem.gen.source
+    calls = re.findall(r"mpcx_net::eval<(\d+), (\d+), (\d+), (\d+), (\w+), (\d+), (\d+)>", src)
+    n = int(re.search(r"#define MPCX_N (\d+)", src).group(1))
+    assert len(calls) == 6   # 2 networks x (fg, gj, hess)
+    for R, nin, H, act, wv, nd1, nd2 in calls:
+        # n: the (super-)stages of the kernel, 8: the horizon
+        assert int(R) > 0 and int(R) % n == 0 and int(R) % 8 == 0
+        assert int(H) == 20 and int(act) == sx.ACT_CODE["tanh"]
+    assert sorted(int(c[1]) for c in calls) == [8, 8, 8, 9, 9, 9]
+    n_in = {}   # network id -> inputs, from the W1T table ([H][n_in])
+    for nid, size in re.findall(r"__constant__ double ANN(\d+)_W1T\[(\d+)\] =", src):
+        n_in[nid] = int(size) // 20
+    tables = re.findall(r"__constant__ int ANN(\d+)_D1(\w+)\[(\d+)\] = \{([^}]*)\}", src)
+    assert tables
+    for nid, kind, size, body in tables:
+        d1 = [int(v) for v in body.split(",")]
+        assert len(d1) == int(size) and d1 == sorted(set(d1)), (nid, kind, d1)
+        assert 0 <= d1[0] and d1[-1] < n_in[nid], (nid, kind, d1, n_in[nid])
+        # the call of this kind and network has as many derivative columns
+        assert any(int(c[5]) == len(d1) and int(c[1]) == n_in[nid] for c in calls)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
