@@ -36,7 +36,7 @@ from agentlib_mpc_amd import symbolic as sx
 from agentlib_mpc_amd.data_structures import ml_model_datatypes as mlt
 from agentlib_mpc_amd.data_structures.ml_model_datatypes import OutputType, name_with_lag
 from agentlib_mpc_amd.models.casadi_model import CasadiModel, CasadiModelConfig, CasadiState
-from agentlib_mpc_amd.models.casadi_predictor import CasadiANN, CasadiPredictor
+from agentlib_mpc_amd.models.casadi_predictor import CasadiANN, CasadiGPR, CasadiLinReg, CasadiPredictor
 from agentlib_mpc_amd.models.serialized_ml_model import SerializedMLModel
 
 logger = logging.getLogger(__name__)
@@ -136,7 +136,7 @@ class CasadiMLModel(CasadiModel):
     def register_ml_models(self):
         by_outputs = {tuple(m.output.keys()): m for m in self.config.ml_model_sources}
         ml_model_dict: Dict[str, SerializedMLModel] = {}
-        casadi_dict: Dict[str, CasadiANN] = {}
+        casadi_dict: Dict[str, Union[CasadiANN, CasadiGPR, CasadiLinReg]] = {}
         for var in self.outputs + self.states:
             for names, m in by_outputs.items():
                 if var.name in names:

@@ -1,4 +1,5 @@
-"""Symbolic forward pass of serialized ANNs (the NARX models of the ML backends).
+"""Symbolic forward pass of serialized ANN, GPR and linear-regression models (the NARX
+models of the ML backends).
 
 Restates the ANN part of `agentlib_mpc/models/casadi_predictor.py`:
 activations (``Layer.get_activation`` :255-299), ``Dense`` (:306-336:
@@ -10,17 +11,23 @@ The input is a row of scalar expressions of the symbolic tracer
 function that the code generator differentiates and emits as straight-line
 HIP; ``predict_numpy`` is the numeric twin used by tests and synthetic-weight
 generation.
+
+``CasadiGPR`` (:113-189) is the posterior mean ``scale * k(x, X_train) @ alpha`` of a
+``ConstantKernel * RBF`` kernel, generalised to scikit-learn's per-feature length scale;
+one opaque RBF network node per output column (:class:`symbolic.RBFNetwork`).
+``CasadiLinReg`` (:87-110) is ``intercept + x @ coef.T``, expanded into the stage graph.
 """
 
 from __future__ import annotations
 
 import math
-from typing import Callable, List, Sequence
+from typing import Callable, List, Sequence, Union
 
 import numpy as np
 
 from agentlib_mpc_amd import symbolic as sx
-from agentlib_mpc_amd.models.serialized_ml_model import SerializedANN, SerializedMLModel
+from agentlib_mpc_amd.models.serialized_ml_model import (SerializedANN, SerializedGPR, SerializedLinReg,
+                                                          SerializedMLModel)
 
 
 def _sigmoid(x):
@@ -175,11 +182,83 @@ def _bn_weights(spec):
             np.asarray(mean).reshape(-1), np.asarray(var).reshape(-1))
 
 
+class CasadiGPR:
+    """GPR mean from a :class:`SerializedGPR` (``CasadiGPR`` of the reference)."""
+
+    def __init__(self, serialized_model: SerializedGPR):
+        self.serialized_model = serialized_model
+        gp, kp, dh = serialized_model.gpr_parameters, serialized_model.kernel_parameters, serialized_model.data_handling
+        if gp is None or kp is None:
+            raise ValueError("a SerializedGPR needs gpr_parameters and kernel_parameters")
+        X = np.asarray(gp.X_train, dtype=float)
+        self.n_in = X.shape[1]
+        alpha = np.asarray(gp.alpha, dtype=float).reshape(X.shape[0], -1)
+        self.n_out = alpha.shape[1]
+        ls = np.broadcast_to(np.asarray(kp.length_scale, dtype=float).reshape(-1), (self.n_in,))
+        mean, std, scale = np.zeros(self.n_in), np.ones(self.n_in), 1.0
+        if dh is not None:
+            scale = float(dh.scale)
+            if dh.normalize:
+                if dh.mean is None or dh.std is None:
+                    raise ValueError("Mean and std are not valid.")
+                mean, std = np.asarray(dh.mean, dtype=float).reshape(-1), np.asarray(dh.std, dtype=float).reshape(-1)
+        # z = s o x + t, T = X_train / l: normalisation and length scale in one affine map
+        self.s = 1.0 / (std * ls)
+        self.t = -mean / (std * ls)
+        self.T = X / ls
+        self.a = scale * float(kp.constant_value) * alpha      # [NT, n_out]
+
+    def _networks(self) -> List[int]:
+        return [sx.register_network(sx.RBFNetwork(self.T, self.a[:, o], self.s, self.t)) for o in range(self.n_out)]
+
+    def predict(self, inputs: Sequence) -> List[sx.Expr]:
+        """One opaque network node per output column."""
+        x = [sx.as_expr(v) for v in inputs]
+        return [sx.ann_call(nid, x) for nid in self._networks()]
+
+    def predict_numpy(self, inputs: np.ndarray) -> np.ndarray:
+        """Mean on rows ``[n, n_in]`` (or one row) -> ``[n, n_out]``."""
+        x = np.atleast_2d(np.asarray(inputs, dtype=float))
+        return np.stack([sx.network(nid).evaluate(x)[0] for nid in self._networks()], axis=1)
+
+
+class CasadiLinReg:
+    """``intercept + x @ coef.T`` from a :class:`SerializedLinReg` (``CasadiLinReg`` of the reference)."""
+
+    def __init__(self, serialized_model: SerializedLinReg):
+        self.serialized_model = serialized_model
+        par = serialized_model.parameters
+        self.coef = np.atleast_2d(np.asarray(par.coef, dtype=float))          # [n_out, n_in]
+        self.n_out, self.n_in = self.coef.shape
+        self.intercept = np.broadcast_to(np.asarray(par.intercept, dtype=float).reshape(-1), (self.n_out,)).copy()
+
+    def predict(self, inputs: Sequence) -> List[sx.Expr]:
+        x = [sx.as_expr(v) for v in inputs]
+        if len(x) != self.n_in:
+            raise ValueError(f"linear regression expects {self.n_in} inputs, got {len(x)}")
+        out = []
+        for o in range(self.n_out):
+            acc = sx.const(float(self.intercept[o]))
+            for i in range(self.n_in):
+                if self.coef[o, i] != 0.0:
+                    acc = sx.add(acc, sx.mul(float(self.coef[o, i]), x[i]))
+            out.append(acc)
+        return out
+
+    def predict_numpy(self, inputs: np.ndarray) -> np.ndarray:
+        x = np.atleast_2d(np.asarray(inputs, dtype=float))
+        return self.intercept + x @ self.coef.T
+
+
 class CasadiPredictor:
     """Factory by model type (`casadi_predictor.py` ``CasadiPredictor.from_serialized_model``)."""
 
     @staticmethod
-    def from_serialized_model(serialized_model: SerializedMLModel) -> CasadiANN:
+    def from_serialized_model(serialized_model: SerializedMLModel) -> Union[CasadiANN, CasadiGPR, CasadiLinReg]:
         if isinstance(serialized_model, SerializedANN):
             return CasadiANN(serialized_model)
-        raise NotImplementedError(f"{type(serialized_model).__name__} is not supported (ANN only)")
+        if isinstance(serialized_model, SerializedGPR):
+            return CasadiGPR(serialized_model)
+        if isinstance(serialized_model, SerializedLinReg):
+            return CasadiLinReg(serialized_model)
+        raise NotImplementedError(f"{type(serialized_model).__name__} is not supported (ANN, GPR and LinReg only)")

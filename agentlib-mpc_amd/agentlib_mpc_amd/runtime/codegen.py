@@ -147,11 +147,20 @@ def factorisation_plan(nlp: StageNLP):
     return [], True
 
 
+#: most training points of an RBF network (GPR model) the generator accepts.  The wave pass
+#: streams the points, so registers and LDS do not grow with them; the bound is on the tables
+#: (T, TT, A as literals in the generated source and lane-indexed reads in the kernel): at 512
+#: points and the 18 inputs of the widest tested network they are 80 KB per network, which two
+#: networks per stage keep resident in L2, and the generated source stays below 2 MB.
+RBF_MAX_POINTS = 512
+
+
 def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emit_h, to_compact):
     """Device code of the network evaluations on the FP64 matrix cores (empty when the
     stage has no network node): ``gen_stage_netin`` (one lane per stage writes the inputs
     of every call site to LDS), ``gen_net_{fg,gj,hess}`` (the wave evaluates each network
-    over all stages x call sites, ``mpcx_net::eval``, csrc/mpcx_net_mfma.h) and the stage
+    over all stages x call sites, ``mpcx_net::eval`` or, for an RBF network,
+    ``mpcx_net::eval_rbf``, csrc/mpcx_net_mfma.h) and the stage
     functions ``gen_stage_{fg,gj,hess}_m`` that read the network entries from LDS instead
     of looping over the hidden units.  Returns (lines, defines, X doubles, output doubles)."""
     sites = {}
@@ -169,6 +178,10 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
     for nid, keys in nets.items():
         xoff[nid] = netx
         netx += N * len(keys) * sx.network(nid).n_in
+        net = sx.network(nid)
+        if isinstance(net, sx.RBFNetwork) and net.NT > RBF_MAX_POINTS:
+            raise ValueError(f"GPR model with {net.NT} training points: the MI355X backend takes at most "
+                             f"{RBF_MAX_POINTS} (codegen.RBF_MAX_POINTS)")
 
     def layout(outs):
         mem = {nid: set() for nid in nets}
@@ -206,7 +219,11 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
             net = sx.network(nid)
             if L["d1"]:
                 lines.append(f"__constant__ int ANN{nid}_D1{kind}[{len(L['d1'])}] = {{{', '.join(map(str, L['d1']))}}};")
-            if L["d2"]:
+            if L["d2"] and isinstance(net, sx.RBFNetwork):
+                # the pair operand T_ja T_jb is formed from two reads of T: only the index pairs
+                p2 = ", ".join(f"{a}, {b}" for a, b in L["d2"])
+                lines.append(f"__constant__ int ANN{nid}_P2{kind}[{2 * len(L['d2'])}] = {{{p2}}};")
+            elif L["d2"]:
                 pw = [net.W1[a, j] * net.W1[b, j] for a, b in L["d2"] for j in range(net.H)]
                 lines.append(f"__constant__ double ANN{nid}_PW{kind}[{len(pw)}] = "
                              f"{{{', '.join(sx._c_literal(float(v)) for v in pw)}}};")
@@ -226,6 +243,13 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
                 continue
             net = sx.network(nid)
             d1 = f"ANN{nid}_D1{kind}" if L["d1"] else "nullptr"
+            if isinstance(net, sx.RBFNetwork):
+                p2 = f"ANN{nid}_P2{kind}" if L["d2"] else "nullptr"
+                lines.append(f"  mpcx_net::eval_rbf<{L['R']}, {net.n_in}, {net.NT}, "
+                             f"{'true' if L['wv'] else 'false'}, {len(L['d1'])}, {len(L['d2'])}>("
+                             f"X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, ANN{nid}_T, ANN{nid}_TT, "
+                             f"ANN{nid}_A, ANN{nid}_S, ANN{nid}_SH, {d1}, {p2}, lane);")
+                continue
             pw = f"ANN{nid}_PW{kind}" if L["d2"] else "nullptr"
             lines.append(f"  mpcx_net::eval<{L['R']}, {net.n_in}, {net.H}, {sx.ACT_CODE[net.act]}, "
                          f"{'true' if L['wv'] else 'false'}, {len(L['d1'])}, {len(L['d2'])}>("

@@ -299,7 +299,7 @@ def default_options() -> Options:
 # ---------------------------------------------------------------------------
 def _kernel_deps_hash() -> str:
     h = hashlib.sha1()
-    for p in (CSRC / "mpcx_ipm.hip", CSRC / "mpcx_internal.h", INCLUDE / "mpcx.h"):
+    for p in (CSRC / "mpcx_ipm.hip", CSRC / "mpcx_internal.h", CSRC / "mpcx_net_mfma.h", INCLUDE / "mpcx.h"):
         h.update(p.read_bytes())
     return h.hexdigest()[:10]
 

@@ -361,6 +361,8 @@ def sum1(items: Iterable) -> Expr:
 # so gradients and Lagrangian Hessians stay compact, and the code generator
 # evaluates each network once per stage in a loop over the hidden units with
 # the weights in constant memory (only the derivative entries that are used).
+# A second interned kind, ``RBFNetwork`` (the mean of a Gaussian process), shares the
+# node names, ``register_network``, ``ann_call`` and the derivative rules.
 
 _ACTS = ("sigmoid", "tanh", "linear", "softplus", "exponential", "gaussian")
 
@@ -410,6 +412,45 @@ class Network:
         g = (s1 * self.w2) @ self.W1.T
         h = np.einsum("...j,ij,kj->...ik", s2 * self.w2, self.W1, self.W1)
         return v, g, h
+
+
+class RBFNetwork:
+    """Mean of a Gaussian process with an RBF kernel, single output: the second network kind.
+
+    ``y(x) = sum_j a_j exp(-1/2 |z - T_j|^2)`` with ``z = s o x + t``: input normalisation and
+    the (per-feature) length scale are folded into ``s``, ``t`` and the table ``T [NT, n_in]``
+    (training points / length scale); ``a_j`` carries the output scale, the kernel's constant
+    and the dual coefficient.  ``tt_j = -1/2 |T_j|^2`` is the table the wave pass starts its
+    accumulators from (csrc/mpcx_net_mfma.h, ``eval_rbf``)."""
+
+    def __init__(self, T: np.ndarray, a: np.ndarray, s: np.ndarray, t: np.ndarray):
+        self.T = np.ascontiguousarray(T, dtype=float)      # [NT, n_in]
+        self.a = np.asarray(a, dtype=float).reshape(-1)
+        self.NT, self.n_in = self.T.shape
+        self.s = np.broadcast_to(np.asarray(s, dtype=float).reshape(-1), (self.n_in,)).copy()
+        self.t = np.broadcast_to(np.asarray(t, dtype=float).reshape(-1), (self.n_in,)).copy()
+        if self.a.shape[0] != self.NT:
+            raise ValueError("one coefficient per training point")
+        self.tt = -0.5 * np.sum(self.T * self.T, axis=1)
+        self.H = self.NT   # terms per evaluation (flop_count)
+
+    def key(self) -> tuple:
+        return ("rbf", self.T.shape, self.T.tobytes(), self.a.tobytes(), self.s.tobytes(), self.t.tobytes())
+
+    def evaluate(self, x: np.ndarray):
+        """value [...], gradient [..., n_in], Hessian [..., n_in, n_in] on rows x [..., n_in]: the
+        algebra of the wave pass in fp64 (expanded distance, moment sums S0, S1, S2)."""
+        z = np.asarray(x, dtype=float) * self.s + self.t
+        e = (z @ self.T.T + self.tt) - 0.5 * np.sum(z * z, axis=-1, keepdims=True)
+        w = self.a * np.exp(e)
+        S0 = w.sum(axis=-1)
+        S1 = w @ self.T
+        S2 = np.einsum("...j,ji,jk->...ik", w, self.T, self.T)
+        g = -self.s * (z * S0[..., None] - S1)
+        zi, zk = z[..., :, None], z[..., None, :]
+        h = (zi * zk * S0[..., None, None] - zi * S1[..., None, :] - zk * S1[..., :, None] + S2
+             - np.eye(self.n_in) * S0[..., None, None]) * (self.s[:, None] * self.s[None, :])
+        return S0, g, h
 
 
 _NETWORKS: List[Network] = []
@@ -888,6 +929,8 @@ def _emit_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
                   names: Dict[int, str], indent: str) -> List[str]:
     """One loop over the hidden units computing the used value/derivative entries."""
     net = _NETWORKS[nid]
+    if isinstance(net, RBFNetwork):
+        return _emit_rbf_network(nid, x, members, gp, names, indent)
     T = f"ANN{nid}"
     nin, H = net.n_in, net.H
     d1 = sorted(i for (k, i, _) in members if k == "d")
@@ -924,11 +967,52 @@ def _emit_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
     return [indent + l for l in L]
 
 
+def _emit_rbf_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
+                      names: Dict[int, str], indent: str) -> List[str]:
+    """One loop over the training points of an RBF network with direct differences
+    ``z_i - T_ji`` (no cancellation on one lane), only the used entries."""
+    net = _NETWORKS[nid]
+    T = f"ANN{nid}"
+    nin, NT = net.n_in, net.NT
+    d1 = sorted(i for (k, i, _) in members if k == "d")
+    d2 = sorted((i, j) for (k, i, j) in members if k == "dd")
+    need_v = ("v", -1, -1) in members
+    L = [f"const double {gp}z{i} = ({x[i]}) * {_c_literal(net.s[i])} + {_c_literal(net.t[i])};" for i in range(nin)]
+    if need_v:
+        L.append(f"double {gp}v = 0.0;")
+    L += [f"double {gp}g{i} = 0.0;" for i in d1]
+    L += [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
+    L.append("#pragma unroll 4")
+    L.append(f"for (int j = 0; j < {NT}; ++j) {{")
+    L += [f"  const double d{i} = {gp}z{i} - {T}_T[j * {nin} + {i}];" for i in range(nin)]
+    L.append(f"  const double w = {T}_A[j] * exp(-0.5 * ({' + '.join(f'd{i} * d{i}' for i in range(nin))}));")
+    if need_v:
+        L.append(f"  {gp}v += w;")
+    L += [f"  {gp}g{i} += w * d{i};" for i in d1]
+    L += [f"  {gp}h{i}_{j} += w * (d{i} * d{j}{' - 1.0' if i == j else ''});" for i, j in d2]
+    L.append("}")
+    L += [f"{gp}g{i} *= {_c_literal(-net.s[i])};" for i in d1]
+    L += [f"{gp}h{i}_{j} *= {_c_literal(net.s[i] * net.s[j])};" for i, j in d2]
+    for (k, i, j), node in members.items():
+        names[node.uid] = f"{gp}v" if k == "v" else (f"{gp}g{i}" if k == "d" else f"{gp}h{i}_{j}")
+    return [indent + l for l in L]
+
+
 def network_tables(net_ids) -> List[str]:
-    """``__constant__`` weight tables of the networks (W1 transposed: [H][n_in])."""
+    """``__constant__`` weight tables of the networks (W1 transposed: [H][n_in]; an RBF
+    network: the training points ``T [NT][n_in]``, the coefficients ``A [NT]``, and for the wave
+    pass ``TT [NT] = -1/2 |T_j|^2`` and the input map ``S``, ``SH`` [n_in])."""
     out = []
     for nid in sorted(net_ids):
         net = _NETWORKS[nid]
+        if isinstance(net, RBFNetwork):
+            lit = lambda v: ", ".join(_c_literal(float(u)) for u in np.asarray(v).reshape(-1))
+            out += [f"__constant__ double ANN{nid}_T[{net.NT * net.n_in}] = {{{lit(net.T)}}};",
+                    f"__constant__ double ANN{nid}_A[{net.NT}] = {{{lit(net.a)}}};",
+                    f"__constant__ double ANN{nid}_TT[{net.NT}] = {{{lit(net.tt)}}};",
+                    f"__constant__ double ANN{nid}_S[{net.n_in}] = {{{lit(net.s)}}};",
+                    f"__constant__ double ANN{nid}_SH[{net.n_in}] = {{{lit(net.t)}}};"]
+            continue
         w1t = ", ".join(_c_literal(v) for v in net.W1.T.reshape(-1))
         b1 = ", ".join(_c_literal(v) for v in net.b1)
         w2 = ", ".join(_c_literal(v) for v in net.w2)

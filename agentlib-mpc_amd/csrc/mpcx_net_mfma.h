@@ -20,6 +20,8 @@
 // hidden units 4r .. 4r + 3 of the two derivative products: no LDS round trip and no
 // lane movement between the three products.
 //
+// eval_rbf below is the same pass for the second network kind (Gaussian-process means).
+//
 // f64 MFMA lane maps (CDNA4): A[m = l & 15][k = l >> 4], B[k = l >> 4][n = l & 15],
 // D lane l register r: [m = (l >> 4) + 4 r][n = l & 15].
 #pragma once
@@ -150,6 +152,152 @@ __device__ __forceinline__ void eval(const ldsd* X, ldsd* V, ldsd* Gd, ldsd* Hd,
         }
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// RBF networks (the mean of a Gaussian process, symbolic.RBFNetwork): R evaluations of
+//
+//   y(x) = sum_j a_j exp(-1/2 |z - T_j|^2),   z = s o x + t
+//
+// Replaces the CasADi graph of the reference's CasadiGPR (casadi_predictor.py:126-174).  With
+// w_j = a_j exp(TT_j + z.T_j - 1/2 |z|^2), TT_j = -1/2 |T_j|^2 (the reference's expanded
+// distance) and the moments S0 = sum w_j, S1_i = sum w_j T_ji, S2_ik = sum w_j T_ji T_jk:
+//
+//   y = S0,  dy/dx_i = -s_i (z_i S0 - S1_i),
+//   d2y/dx_i dx_k = s_i s_k (z_i z_k S0 - z_i S1_k - z_k S1_i + S2_ik - delta_ik S0)
+//
+// The first product is transposed as in eval (training point on the accumulator row,
+// evaluation on the lane; accumulators start from TT in the role of B1, B = z formed from the
+// LDS inputs), so register r of lane l holds the weight of training point 4r + (l >> 4) of
+// the tile for evaluation l & 15: the B operand of the moment products.  The training points
+// are streamed in tiles of 16: per tile the value and the moment accumulators are updated and
+// the weights dropped, so register use does not depend on NT.  A Hessian entry (a, b) needs
+// S1_a and S1_b whether or not the gradient list holds them: every pair tile carries three
+// accumulators (S2_ab, S1_a, S1_b; A operands T_ja T_jb from two table reads, T_ja, T_jb),
+// which land in the lane and register of the entry they belong to.  Rows of the last tile
+// past NT get the weight 0 exactly (a is read as 0 there; exp of their finite exponent is
+// finite).  The exponent is <= 0 up to rounding: no overflow guard; far from the data the
+// weights underflow to 0 and every output is 0.
+//
+// X[R][NIN] (LDS) -> V[R] (if WV), Gd[R][ND1] (inputs D1[]), Hd[R][ND2] (pairs P2[ND2][2]).
+// T[NT][NIN], TT[NT], A[NT], S[NIN], SH[NIN]: tables of the network.
+template <int R, int NIN, int NT, bool WV, int ND1, int ND2>
+__device__ __forceinline__ void eval_rbf(const ldsd* X, ldsd* V, ldsd* Gd, ldsd* Hd, const double* T,
+                                         const double* TT, const double* A, const double* S,
+                                         const double* SH, const int* D1, const int* P2, int lane) {
+  constexpr int JT = (NT + 15) / 16;   // training-point tiles
+  constexpr int KS = (NIN + 3) / 4;    // k-steps over the inputs
+  constexpr int GT = (ND1 + 15) / 16, PT = (ND2 + 15) / 16;
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll 1
+  for (int rt = 0; rt < (R + 15) / 16; ++rt) {
+    const int row = rt * 16 + lr;
+    // B operand of the first product and |z|^2 of the row (partial sums over the lane's inputs)
+    double bz[KS];
+    double zz = 0.0;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int i = ks * 4 + lk;
+      bz[ks] = (row < R && i < NIN) ? X[row * NIN + i] * S[i] + SH[i] : 0.0;
+      zz += bz[ks] * bz[ks];
+    }
+    zz += __shfl_xor(zz, 16, 64);
+    zz += __shfl_xor(zz, 32, 64);
+    const double hz = 0.5 * zz;
+    double v = 0.0;
+    d4 g[GT > 0 ? GT : 1], h2[PT > 0 ? PT : 1], ha[PT > 0 ? PT : 1], hb[PT > 0 ? PT : 1];
+    int gcol[GT > 0 ? GT : 1], pa[PT > 0 ? PT : 1], pb[PT > 0 ? PT : 1];
+#pragma unroll
+    for (int it = 0; it < GT; ++it) {
+      g[it] = d4{0.0, 0.0, 0.0, 0.0};
+      gcol[it] = it * 16 + lr < ND1 ? D1[it * 16 + lr] : 0;
+    }
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) {
+      h2[pt] = ha[pt] = hb[pt] = d4{0.0, 0.0, 0.0, 0.0};
+      const int pp = pt * 16 + lr;
+      pa[pt] = pp < ND2 ? P2[2 * pp] : 0;
+      pb[pt] = pp < ND2 ? P2[2 * pp + 1] : 0;
+    }
+#pragma unroll 1
+    for (int jt = 0; jt < JT; ++jt) {
+      d4 acc;
+      double w[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = jt * 16 + lk + 4 * r;
+        acc[r] = j < NT ? TT[j] : 0.0;
+      }
+      const int jj = jt * 16 + lr;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const int i = ks * 4 + lk;
+        const double aw = (jj < NT && i < NIN) ? T[jj * NIN + i] : 0.0;
+        acc = mfma(aw, bz[ks], acc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = jt * 16 + lk + 4 * r;
+        w[r] = (j < NT ? A[j] : 0.0) * exp(acc[r] - hz);
+        v += w[r];
+      }
+#pragma unroll
+      for (int it = 0; it < GT; ++it)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int j = jt * 16 + 4 * r + lk;
+          const double aw = (it * 16 + lr < ND1 && j < NT) ? T[j * NIN + gcol[it]] : 0.0;
+          g[it] = mfma(aw, w[r], g[it]);
+        }
+#pragma unroll
+      for (int pt = 0; pt < PT; ++pt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int j = jt * 16 + 4 * r + lk;
+          const bool on = pt * 16 + lr < ND2 && j < NT;
+          const double ta = on ? T[j * NIN + pa[pt]] : 0.0;
+          const double tb = on ? T[j * NIN + pb[pt]] : 0.0;
+          h2[pt] = mfma(ta * tb, w[r], h2[pt]);
+          ha[pt] = mfma(ta, w[r], ha[pt]);
+          hb[pt] = mfma(tb, w[r], hb[pt]);
+        }
+    }
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);   // S0 of the row, in its four lanes
+    if constexpr (WV)
+      if (lk == 0 && row < R) V[row] = v;
+#pragma unroll
+    for (int it = 0; it < GT; ++it)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = it * 16 + lk + 4 * r;
+        if (o < ND1 && row < R) {
+          const int i = D1[o];
+          const double zi = X[row * NIN + i] * S[i] + SH[i];
+          // the product rounded on its own (no fma): on a model's only training point the
+          // gradient is exactly 0, as in the fp64 evaluation
+          double zv;
+          {
+#pragma clang fp contract(off)
+            zv = zi * v;
+          }
+          Gd[row * ND1 + o] = -S[i] * (zv - g[it][r]);
+        }
+      }
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = pt * 16 + lk + 4 * r;
+        if (o < ND2 && row < R) {
+          const int a = P2[2 * o], b = P2[2 * o + 1];
+          const double za = X[row * NIN + a] * S[a] + SH[a];
+          const double zb = X[row * NIN + b] * S[b] + SH[b];
+          const double m = za * zb * v - za * hb[pt][r] - zb * ha[pt][r] + h2[pt][r] - (a == b ? v : 0.0);
+          Hd[row * ND2 + o] = S[a] * S[b] * m;
+        }
+      }
   }
 }
 
