@@ -17,7 +17,7 @@ import shutil
 import subprocess
 import threading
 import warnings
-from typing import List, Dict, Optional
+from typing import Callable, List, Dict, NamedTuple, Optional, Tuple
 
 PKG_DIR = pathlib.Path(__file__).resolve().parents[1]          # agentlib_mpc_amd/
 ROOT_DIR = PKG_DIR.parent                                       # agentlib-mpc_amd/
@@ -102,7 +102,7 @@ ADMM_TOTALS = 8  # MPCX_ADMM_TOTALS
 ADMM_CONTROL = 1  # MPCX_ADMM_CONTROL: control doubles before the moments buffer (C ABI v10)
 RCCL_ID_BYTES = 128  # MPCX_RCCL_ID_BYTES
 COLLECTIVE_NONE, COLLECTIVE_RCCL, COLLECTIVE_FN = 0, 1, 2  # mpcx_allreduce_kind
-ERR_ARG, ERR_COMM = -1, -6  # MPCX_ERR_ARG, MPCX_ERR_COMM
+ERR_ARG, ERR_MODULE, ERR_COMM = -1, -3, -6  # MPCX_ERR_ARG, MPCX_ERR_MODULE, MPCX_ERR_COMM
 #: mpcx_allreduce_fn: int (*)(void* ctx, double* buf, int64_t count, void* stream)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
 KERNEL_ABI = 8  # MPCX_KERNEL_ABI (csrc/mpcx_internal.h)
@@ -122,7 +122,7 @@ def build_library(force: bool = False) -> pathlib.Path:
     """Compile libmpcx.so (host runtime + ADMM kernels) for gfx950, in-tree."""
     BUILD_DIR.mkdir(parents=True, exist_ok=True)
     srcs = [CSRC / "mpcx_runtime.cpp", CSRC / "admm_kernels.hip", CSRC / "mpcx_collective.cpp"]
-    deps = srcs + [INCLUDE / "mpcx.h", CSRC / "mpcx_internal.h"]
+    deps = srcs + [INCLUDE / "mpcx.h", CSRC / "mpcx_internal.h", CSRC / "mpcx_builds.h"]
     if LIB_PATH.exists() and not force:
         if LIB_PATH.stat().st_mtime >= max(p.stat().st_mtime for p in deps):
             return LIB_PATH
@@ -197,9 +197,8 @@ def load_library():
         lib.mpcx_set_options.argtypes = [vp, ctypes.POINTER(Options)]
         lib.mpcx_reserve.argtypes = [vp, i32]
         lib.mpcx_workspace_bytes_per_agent.argtypes = [vp]
-        lib.mpcx_problem_small_fleet.argtypes = [vp, ctypes.c_char_p, i32]
-        lib.mpcx_problem_mid_fleet.argtypes = [vp, ctypes.c_char_p, i32]
-        lib.mpcx_problem_wide_fleet.argtypes = [vp, ctypes.c_char_p, i32]
+        for v in VARIANTS:
+            getattr(lib, v.cfunc).argtypes = [vp, ctypes.c_char_p, i32]
         lib.mpcx_workspace_bytes_per_agent.restype = ctypes.c_int64
         lib.mpcx_admm_block_expand_multi.argtypes = [i32, vp, i32, vp, vp, vp]
         lib.mpcx_stats_count_multi.argtypes = [i32, vp, i32, vp, vp]
@@ -323,8 +322,39 @@ WIDE_SCRATCH_MAX = 128
 #: compiler messages of the kernel's own static_asserts that mean "this structure does not fit
 #: the variant" (permanent for the code object's source hash)
 _NOFIT_MESSAGES = ("workspace does not fit LDS", "LDS share per agent exceeded")
-_VARIANT_DEFINES = {None: [], SMALL_FLEET: ["MPCX_WS_LDS"], MID_FLEET: ["MPCX_MIN_WAVES=1"],
-                    WIDE_FLEET: ["MPCX_APC=20"]}
+
+
+class Variant(NamedTuple):
+    """An optional build beside the main one: how it is compiled, when, and how it is attached
+    (its slot and routing rule: csrc/mpcx_builds.h, mpcx_runtime.cpp)."""
+    key: str                # ``variant`` of compile_model, tag of the code object's name
+    defines: Tuple[str, ...]
+    label: str              # in warnings and build logs
+    env: str                # ``<env>=0`` in the environment: NativeProblem does not attach it
+    cfunc: str              # attaches a code object / sets the limit (include/mpcx.h)
+    short: str              # NativeProblem.select_build's name for it
+    fallback: str           # the build named when attaching fails
+    every: int              # the limit that routes every batch size to it
+    #: compiled only where the main build's occupancy (waves per SIMD, its ``.occ`` file) passes
+    #: the test; else the text goes into the ``.nofit`` marker
+    main_occ: Optional[Tuple[Callable[[int], bool], str]] = None
+    scratch_max: Optional[int] = None   # largest call-frame scratch (B/lane) of the build
+
+
+#: in routing order: small fleets (one generation of workgroups with the workspace in LDS), fleets
+#: of at most one agent per SIMD, fleets of more than one generation of a 16-per-CU main build
+VARIANTS = (
+    Variant(SMALL_FLEET, ("MPCX_WS_LDS",), "small-fleet", "MPCX_SMALL_FLEET", "mpcx_problem_small_fleet",
+            "lds", "HBM", 1 << 30),
+    Variant(MID_FLEET, ("MPCX_MIN_WAVES=1",), "one-wave-per-SIMD", "MPCX_MID_FLEET", "mpcx_problem_mid_fleet",
+            "mid", "main", 1 << 30,
+            main_occ=(lambda occ: occ > 1, "the main build already runs one wave per SIMD")),
+    Variant(WIDE_FLEET, ("MPCX_APC=20",), "20-agents-per-CU", "MPCX_WIDE_FLEET", "mpcx_problem_wide_fleet",
+            "wide", "main", 1,
+            main_occ=(lambda occ: occ == 4, "the main build does not hold 16 agents per CU"),
+            scratch_max=WIDE_SCRATCH_MAX),
+)
+_BY_KEY = {v.key: v for v in VARIANTS}
 
 
 def code_object_path(gen_key: str, variant: Optional[str] = None) -> pathlib.Path:
@@ -345,9 +375,8 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
     nofit = out.with_suffix(".nofit")
     if variant is not None and nofit.exists():
         return None
-    if variant in (MID_FLEET, WIDE_FLEET):
-        # MID_FLEET only where the main build's register budget is tighter than one wave per SIMD,
-        # WIDE_FLEET only where the main build holds 16 agents per CU (four waves per SIMD)
+    v = _BY_KEY[variant] if variant is not None else None
+    if v is not None and v.main_occ is not None:
         base = compile_model(gen, verbose)
         occ = base.with_suffix(".occ")
         if not occ.exists():
@@ -355,16 +384,14 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
             # marker, so the decision is taken again once the occupancy is known
             warnings.warn(f"occupancy of {base.name} unknown; no one-wave-per-SIMD build this time")
             return None
-        if variant == MID_FLEET and int(occ.read_text() or "1") <= 1:
-            nofit.write_text("the main build already runs one wave per SIMD")
-            return None
-        if variant == WIDE_FLEET and int(occ.read_text() or "0") != 4:
-            nofit.write_text("the main build does not hold 16 agents per CU")
+        fits, reason = v.main_occ
+        if not fits(int(occ.read_text() or "0")):
+            nofit.write_text(reason)
             return None
     src = out.with_suffix(".hip")
     src.write_text(gen.source)
     tmp = out.with_suffix(".tmp")
-    defs = _extra_defines() + _VARIANT_DEFINES[variant]
+    defs = _extra_defines() + list(v.defines if v is not None else ())
     cmd = [_hipcc(), "--genco", f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17",
            f"-I{INCLUDE}", f"-I{CSRC}", *[f"-D{d}" for d in defs], str(src), "-o", str(tmp),
            "-Rpass-analysis=kernel-resource-usage"]
@@ -378,9 +405,7 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
             if any(m in res.stderr for m in _NOFIT_MESSAGES):
                 nofit.write_text(res.stderr[-4000:])
             else:
-                name = {SMALL_FLEET: "small-fleet", MID_FLEET: "one-wave-per-SIMD",
-                        WIDE_FLEET: "20-agents-per-CU"}.get(variant, variant)
-                warnings.warn(f"{name} build of {gen.key} failed; the main build serves every batch:\n"
+                warnings.warn(f"{v.label} build of {gen.key} failed; the main build serves every batch:\n"
                               f"{res.stderr[-800:]}")
             tmp.unlink(missing_ok=True)
             return None
@@ -393,12 +418,12 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
             out.with_suffix(".occ").write_text(occ.group(1))
         else:  # remark format changed: leave the decision open rather than never building w1
             warnings.warn(f"no occupancy remark for mpcx_ipm_solve in the build of {out.name}")
-    if variant == WIDE_FLEET:
+    if v is not None and v.scratch_max is not None:
         scr = re.search(r"Function Name: mpcx_ipm_solve.*?ScratchSize \[bytes/lane\]: (\d+)", res.stderr, re.S)
-        if scr is None or int(scr.group(1)) > WIDE_SCRATCH_MAX:
+        if scr is None or int(scr.group(1)) > v.scratch_max:
             # permanent for this source hash when measured; an unreadable remark is retried
             if scr is not None:
-                nofit.write_text(f"scratch {scr.group(1)} B/lane > {WIDE_SCRATCH_MAX}")
+                nofit.write_text(f"scratch {scr.group(1)} B/lane > {v.scratch_max}")
             else:
                 warnings.warn(f"no scratch remark for mpcx_ipm_solve in the build of {out.name}")
             tmp.unlink(missing_ok=True)
@@ -424,38 +449,15 @@ class NativeProblem:
         if rc != 0:
             raise NativeError(f"mpcx_problem_create failed ({rc}) for {path}")
         self.handle = handle
-        self.small_fleet_path = None
-        if hsaco is None and os.environ.get("MPCX_SMALL_FLEET", "1") != "0":
-            # small fleets (<= one agent per CU) run the workspace-in-LDS build when the
-            # structure's workspace fits a CU's LDS (compiled by build(), else here)
-            sp = compile_model(gen, variant=SMALL_FLEET)
-            if sp is not None:
-                rc = self.lib.mpcx_problem_small_fleet(handle, str(sp).encode(), -1)
-                if rc != 0:  # optional: the HBM build (loaded above) serves every batch size
-                    warnings.warn(f"mpcx_problem_small_fleet failed ({rc}) for {sp}; using the HBM build")
-                else:
-                    self.small_fleet_path = sp
-        self.mid_fleet_path = None
-        if hsaco is None and os.environ.get("MPCX_MID_FLEET", "1") != "0":
-            # fleets of at most one agent per SIMD run the build with that register budget
-            mp = compile_model(gen, variant=MID_FLEET)
-            if mp is not None:
-                rc = self.lib.mpcx_problem_mid_fleet(handle, str(mp).encode(), -1)
-                if rc != 0:  # optional, as the small-fleet build
-                    warnings.warn(f"mpcx_problem_mid_fleet failed ({rc}) for {mp}; using the main build")
-                else:
-                    self.mid_fleet_path = mp
-        self.wide_fleet_path = None
-        if hsaco is None and os.environ.get("MPCX_WIDE_FLEET", "1") != "0":
-            # fleets of more than one generation of a 16-agents-per-CU main build run the
-            # 20-agents-per-CU build where its spills stay small
-            wp = compile_model(gen, variant=WIDE_FLEET)
-            if wp is not None:
-                rc = self.lib.mpcx_problem_wide_fleet(handle, str(wp).encode(), -1)
-                if rc != 0:  # optional, as the other builds
-                    warnings.warn(f"mpcx_problem_wide_fleet failed ({rc}) for {wp}; using the main build")
-                else:
-                    self.wide_fleet_path = wp
+        #: code object attached per optional build (VARIANTS key), None where there is none
+        self.build_paths = {v.key: None for v in VARIANTS}
+        for v in VARIANTS:
+            if hsaco is not None or os.environ.get(v.env, "1") == "0":
+                continue
+            vp = compile_model(gen, variant=v.key)  # compiled by build(), else here
+            if vp is not None and (rc := self.attach_build(v.key, vp)) != 0:
+                # optional: the main build (loaded above) serves every batch size
+                warnings.warn(f"{v.cfunc} failed ({rc}) for {vp}; using the {v.fallback} build")
         self.options = default_options()
         self.nw = d["NX"] + d["N"] * (d["NV"] + d["NX"])
         self.ng_total = d["N"] * d["NG"]
@@ -480,26 +482,48 @@ class NativeProblem:
         if rc != 0:
             raise NativeError(f"mpcx_set_options failed ({rc})")
 
+    small_fleet_path = property(lambda self: self.build_paths[SMALL_FLEET])
+    mid_fleet_path = property(lambda self: self.build_paths[MID_FLEET])
+    wide_fleet_path = property(lambda self: self.build_paths[WIDE_FLEET])
+
+    def attach_build(self, variant: str, path) -> int:
+        """Hand a code object to the slot of ``variant`` (a VARIANTS key) at its default limit;
+        the C ABI's return code (``ERR_MODULE``: not such a build, the slot keeps what it had)."""
+        rc = getattr(self.lib, _BY_KEY[variant].cfunc)(self.handle, str(path).encode(), -1)
+        if rc == 0:
+            self.build_paths[variant] = pathlib.Path(path)
+        return rc
+
+    def set_build_limit(self, variant: str, n: int):
+        """The batch size up to (wide: from) which the build ``variant`` (a VARIANTS key) is
+        launched: -1 its default, 0 never."""
+        cfunc = _BY_KEY[variant].cfunc
+        rc = getattr(self.lib, cfunc)(self.handle, None, int(n))
+        if rc != 0:
+            raise NativeError(f"{cfunc} failed ({rc})")
+
+    def select_build(self, name: Optional[str]):
+        """Route every batch size to one code object: ``"lds"``, ``"mid"``, ``"wide"`` (the
+        ``short`` names of VARIANTS) or ``"main"``; None restores the default limits."""
+        if name not in (None, "main", *(v.short for v in VARIANTS if self.build_paths[v.key] is not None)):
+            raise NativeError(f"no build {name!r} is loaded for this structure")
+        for v in VARIANTS:
+            self.set_build_limit(v.key, -1 if name is None else v.every if name == v.short else 0)
+
     def set_small_fleet_max(self, max_agents: int):
         """Largest batch launched on the small-fleet (workspace-in-LDS) build: -1 one generation
         (the CU count times the agents a CU's LDS holds of that build, at most four; default),
         0 never."""
-        rc = self.lib.mpcx_problem_small_fleet(self.handle, None, int(max_agents))
-        if rc != 0:
-            raise NativeError(f"mpcx_problem_small_fleet failed ({rc})")
+        self.set_build_limit(SMALL_FLEET, max_agents)
 
     def set_mid_fleet_max(self, max_agents: int):
         """Largest batch launched on the one-wave-per-SIMD build: -1 four per CU (default), 0 never."""
-        rc = self.lib.mpcx_problem_mid_fleet(self.handle, None, int(max_agents))
-        if rc != 0:
-            raise NativeError(f"mpcx_problem_mid_fleet failed ({rc})")
+        self.set_build_limit(MID_FLEET, max_agents)
 
     def set_wide_fleet_min(self, min_agents: int):
         """Smallest batch launched on the 20-agents-per-CU build: -1 more than one generation of
         the main build (default), 0 never."""
-        rc = self.lib.mpcx_problem_wide_fleet(self.handle, None, int(min_agents))
-        if rc != 0:
-            raise NativeError(f"mpcx_problem_wide_fleet failed ({rc})")
+        self.set_build_limit(WIDE_FLEET, min_agents)
 
     def workspace_bytes_per_agent(self) -> int:
         return int(self.lib.mpcx_workspace_bytes_per_agent(self.handle))

@@ -21,7 +21,7 @@ def main():
     import bench
     from agentlib_mpc_amd import benchmarks as bm
     from agentlib_mpc_amd.optimization_backends.problem import fleet_nlp_inputs
-    from agentlib_mpc_amd.runtime.native import STATS_BYTES, stats_array
+    from agentlib_mpc_amd.runtime.native import STATS_BYTES, NativeError, stats_array
 
     model = os.environ.get("MODEL", "one_room")
     sizes = [int(v) for v in os.environ.get("SIZES", "1,256,512,1024,2048,4096").split(",")]
@@ -44,10 +44,10 @@ def main():
         native.reserve(n)
         ref = None
         for b in builds:
-            if b == "lds" and native.small_fleet_path is None or b == "mid" and native.mid_fleet_path is None:
+            try:
+                native.select_build(b)
+            except NativeError:  # no such build for this structure
                 continue
-            native.set_small_fleet_max(1 << 30 if b == "lds" else 0)
-            native.set_mid_fleet_max(1 << 30 if b == "mid" else 0)
             tw = tw0.clone()
             st = torch.zeros(n * STATS_BYTES, dtype=torch.uint8, device=dev)
             s = torch.cuda.current_stream()
@@ -69,8 +69,7 @@ def main():
             print(json.dumps({"model": model, "agents": n, "agents_per_cu": n / cus, "build": b,
                               "kernel_ms": e0.elapsed_time(e1) / reps, "mean_iter": float(arr["iter_count"].mean()),
                               "same_status_iters_as_first": same}), flush=True)
-        native.set_small_fleet_max(-1)
-        native.set_mid_fleet_max(-1)
+        native.select_build(None)
 
 
 if __name__ == "__main__":

@@ -34,8 +34,7 @@ def main():
     be, cv = getattr(bm, model)(solver_options=bm.REFERENCE)
     prob = be.problem
     native = be._native()
-    native.set_small_fleet_max(0)
-    native.set_mid_fleet_max(0)
+    native.select_build("main")
     lds = int(os.environ["LDS"])
     dev = torch.device("cuda")
     if model == "one_room":

@@ -67,6 +67,7 @@ def build(names):
 
 def run(names):
     from oracle import ipm
+    from agentlib_mpc_amd.runtime.native import SMALL_FLEET
     from tests.test_gpu_ipm import _w_of
     ks = [int(x) for x in os.environ.get("KS", "10,15,20,25,30,35,40,45,50,55,60,65,70,100").split(",")]
     for k in ks:
@@ -79,11 +80,9 @@ def run(names):
         for name in names:
             case = case_of(opts)
             nat = case.backend._native()
-            rc = nat.lib.mpcx_problem_small_fleet(nat.handle, str(vdir() / f"{BUILD}_{name}.hsaco").encode(), -1)
+            rc = nat.attach_build(SMALL_FLEET, vdir() / f"{BUILD}_{name}.hsaco")
             assert rc == 0, (name, rc)
-            nat.set_small_fleet_max(1 << 30)
-            nat.set_mid_fleet_max(0)
-            nat.set_wide_fleet_min(0)
+            nat.select_build("lds")
             r = case.backend.solve_batch(0.0, [case.current_vars])[0]
             st = r.stats
             w = _w_of(case, r)
@@ -111,9 +110,7 @@ def dist(builds):
     T = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)  # noqa: E731
     nat = case.backend._native()
     for b in builds or ["lds", "mid", "main"]:
-        nat.set_small_fleet_max(1 << 30 if b == "lds" else 0)
-        nat.set_mid_fleet_max(1 << 30 if b == "mid" else 0)
-        nat.set_wide_fleet_min(0)
+        nat.select_build(b)
         nat.set_options(**REF)
         nat.reserve(n)
         tw = T(kw)
@@ -133,16 +130,16 @@ def trace(draws):
     line-search trials (kernel), refinement steps (both)."""
     import torch
     from oracle import ipm
-    from agentlib_mpc_amd.runtime.native import STATS_BYTES, stats_to_dicts
+    from agentlib_mpc_amd.runtime.native import SMALL_FLEET, STATS_BYTES, stats_to_dicts
     from tests.test_multi_minima import perturbed
     case = case_of(REF)
     p, lbw, ubw, w0 = case.oracle_inputs
     dev = torch.device("cuda")
     T = lambda a: torch.as_tensor(np.ascontiguousarray(a)[None], device=dev)  # noqa: E731
     nat = case.backend._native()
-    rc = nat.lib.mpcx_problem_small_fleet(nat.handle, str(vdir() / "lds_trace.hsaco").encode(), -1)
+    rc = nat.attach_build(SMALL_FLEET, vdir() / "lds_trace.hsaco")
     assert rc == 0, rc
-    nat.set_small_fleet_max(1 << 30)
+    nat.select_build("lds")
     nat.set_options(**REF)
     nat.reserve(1)
     for d in [int(x) for x in draws]:

@@ -60,15 +60,11 @@ def select_build(native, build):
         pytest.skip("no one-wave-per-SIMD build for this structure (its main build runs one wave per SIMD)")
     if build == "wide" and native.wide_fleet_path is None:
         pytest.skip("no 20-agents-per-CU build for this structure")
-    native.set_small_fleet_max(1 << 30 if build == "lds" else 0)
-    native.set_mid_fleet_max(1 << 30 if build == "mid" else 0)
-    native.set_wide_fleet_min(1 if build == "wide" else 0)
+    native.select_build(build)
 
 
 def reset_builds(native):
-    native.set_small_fleet_max(-1)
-    native.set_mid_fleet_max(-1)
-    native.set_wide_fleet_min(-1)
+    native.select_build(None)
 
 
 def _gpu_solve(case, n_copies=1, build="lds"):
@@ -695,3 +691,51 @@ def test_gpu_mid_fleet_build_matches_main_build():
     assert [s["iter_count"] for s in sm] == [s["iter_count"] for s in sb]
     assert np.mean([s["status"] in (0, 1) for s in sm]) > 0.99
     np.testing.assert_allclose(wm, wb, rtol=1e-9, atol=1e-10)
+
+
+def test_gpu_optional_build_slots_reject_the_wrong_code_object():
+    """What each slot of the optional builds accepts (mpcx_runtime.cpp): the small slot only a
+    workspace-in-LDS object, the mid slot only an HBM one for one wave per SIMD, the wide slot only
+    an HBM one with more agents per CU than the main build.  A rejected object returns
+    ``ERR_MODULE`` and leaves the slot as it was: three C1 agents solved on the small-fleet build
+    before and after are bit-identical (``w`` and the stats bytes), and again after every slot was
+    closed (``select_build("main")``) and the defaults restored (``select_build(None)``)."""
+    import bench
+    from agentlib_mpc_amd import benchmarks as bm
+    from agentlib_mpc_amd.optimization_backends.problem import fleet_nlp_inputs
+    from agentlib_mpc_amd.runtime import native as nat
+
+    n = 3
+    be, cv = bm.one_room(solver_options=bm.REFERENCE)
+    p, lbw, ubw, w0 = be.problem.to_kernel(*fleet_nlp_inputs(be.problem, cv, bench.fleet_values(n, 20261015 + 5)))
+    native = be._native()
+    T = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
+
+    def solve():
+        tw = T(w0)
+        st = torch.zeros(n * nat.STATS_BYTES, dtype=torch.uint8, device="cuda")
+        native.solve(T(p), T(lbw), T(ubw), tw, stats=st)
+        torch.cuda.synchronize()
+        return tw.cpu().numpy(), st.cpu().numpy()
+
+    main_path, small_path = nat.code_object_path(be.problem.gen.key), native.small_fleet_path
+    assert small_path is not None, "one_room's workspace fits LDS: the small-fleet build must load"
+    try:
+        native.select_build("lds")
+        w1, s1 = solve()
+        assert np.isfinite(w1).all() and not np.array_equal(w1, w0)
+        assert native.attach_build(nat.SMALL_FLEET, main_path) == nat.ERR_MODULE
+        assert native.attach_build(nat.MID_FLEET, small_path) == nat.ERR_MODULE
+        assert native.attach_build(nat.WIDE_FLEET, main_path) == nat.ERR_MODULE
+        assert native.small_fleet_path == small_path
+        w2, s2 = solve()
+        np.testing.assert_array_equal(w2, w1)
+        np.testing.assert_array_equal(s2, s1)
+        native.select_build("main")
+        native.select_build(None)
+        assert native.small_fleet_path == small_path
+        w3, s3 = solve()  # three agents: the default routing takes the small-fleet build
+        np.testing.assert_array_equal(w3, w1)
+        np.testing.assert_array_equal(s3, s1)
+    finally:
+        native.select_build(None)

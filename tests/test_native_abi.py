@@ -202,3 +202,121 @@ def test_one_wave_per_simd_build_only_where_the_main_build_is_tighter():
     gen = bm.mhe_room()[0].problem.gen
     assert native.compile_model(gen, variant=native.MID_FLEET) is None
     assert int(native.code_object_path(gen.key).with_suffix(".occ").read_text()) == 1
+
+
+# ---------------------------------------------------------------------------
+# the optional builds: one table (native.VARIANTS), one routing rule (csrc/mpcx_builds.h)
+# ---------------------------------------------------------------------------
+
+_ROUTE_MAIN = """
+#include <cstdio>
+#include "mpcx_builds.h"
+int main() {
+  static const char* const names[] = {"small", "mid", "wide", "main"};
+  static_assert(mpcx_builds::SMALL == 0 && mpcx_builds::MID == 1 && mpcx_builds::WIDE == 2 &&
+                mpcx_builds::MAIN == 3 && mpcx_builds::N_SLOTS == 3, "routing order");
+  int limit[3], ld[3], n;
+  while (std::scanf("%d %d %d %d %d %d %d", &limit[0], &limit[1], &limit[2], &ld[0], &ld[1], &ld[2], &n) == 7) {
+    const bool loaded[3] = {ld[0] != 0, ld[1] != 0, ld[2] != 0};
+    std::printf("%s\\n", names[mpcx_builds::route(limit, loaded, n)]);
+  }
+  return 0;
+}
+"""
+
+#: ((small, mid, wide limits), (loaded flags), n_launch, the build the parent's ternary chose)
+_ROUTE_CASES = [
+    *[((256, 1024, 4097), (1, 1, 1), n, b) for n, b in
+      [(1, "small"), (256, "small"), (257, "mid"), (1024, "mid"), (1025, "main"), (4096, "main"),
+       (4097, "wide"), (100000, "wide")]],
+    ((0, 1024, 4097), (0, 1, 1), 1, "mid"),            # nothing in the small slot: its limit is 0
+    ((256, 1024, 0), (1, 1, 1), 100000, "main"),       # wide closed
+    ((0, 0, 1), (1, 1, 1), 1, "wide"),                 # every batch size to the wide build
+    *[((0, 0, 0), (1, 1, 1), n, "main") for n in (1, 256, 4097, 100000)],
+    *[((0, 0, 0), (0, 0, 0), n, "main") for n in (1, 100000)],
+    ((5000, 1024, 4097), (1, 1, 1), 4500, "small"),    # overlap: the order decides
+]
+
+
+def test_routing_rule_matches_the_nested_ternary(tmp_path):
+    """``mpcx_builds::route`` (csrc/mpcx_builds.h, no HIP) compiled alone with the host compiler:
+    small, then mid (``n <= limit``), then wide (``limit > 0 and n >= limit``), then main."""
+    import os
+    import shutil
+    import subprocess
+
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    src = tmp_path / "route_main.cpp"
+    src.write_text(_ROUTE_MAIN)
+    exe = tmp_path / "route_main"
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{native.CSRC}", str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True)
+    lines = "".join(f"{' '.join(map(str, lim))} {' '.join(map(str, ld))} {n}\n" for lim, ld, n, _ in _ROUTE_CASES)
+    got = subprocess.run([str(exe)], input=lines, check=True, capture_output=True, text=True).stdout.split()
+    assert got == [b for *_, b in _ROUTE_CASES]
+
+
+def test_variant_table_agrees_with_the_header():
+    names = declared_functions()
+    assert [v.cfunc for v in native.VARIANTS] == ["mpcx_problem_small_fleet", "mpcx_problem_mid_fleet",
+                                                  "mpcx_problem_wide_fleet"]  # routing order
+    for v in native.VARIANTS:
+        assert v.cfunc in names, v
+    assert [v.key for v in native.VARIANTS] == [native.SMALL_FLEET, native.MID_FLEET, native.WIDE_FLEET]
+    assert [v.short for v in native.VARIANTS] == ["lds", "mid", "wide"]
+    assert [v.scratch_max for v in native.VARIANTS] == [None, None, native.WIDE_SCRATCH_MAX]
+    text = HEADER.read_text()
+    for name, value in (("ARG", native.ERR_ARG), ("MODULE", native.ERR_MODULE)):
+        assert int(re.search(rf"MPCX_ERR_{name} = (-?\d+)", text).group(1)) == value
+
+
+@pytest.mark.parametrize("variant,defines", [(None, []), ("wslds", ["-DMPCX_WS_LDS"]),
+                                             ("w1", ["-DMPCX_MIN_WAVES=1"]), ("apc20", ["-DMPCX_APC=20"])])
+def test_compile_model_command_line(tmp_path, monkeypatch, variant, defines):
+    """The hipcc command of every build, argument for argument (the defines written out here)."""
+    import types
+
+    from agentlib_mpc_amd import benchmarks as bm
+
+    gen = bm.one_room()[0].problem.gen
+    monkeypatch.setattr(native, "KERNEL_DIR", tmp_path)
+    monkeypatch.setattr(native, "_hipcc", lambda: "hipcc-under-test")
+    monkeypatch.delenv("MPCX_DEFINES", raising=False)
+    cmds = []
+
+    def fake_run(cmd, **kw):
+        cmds.append(cmd)
+        return types.SimpleNamespace(returncode=1, stderr="killed")
+    monkeypatch.setattr(native.subprocess, "run", fake_run)
+    if variant is None:
+        with pytest.raises(native.NativeError):
+            native.compile_model(gen)
+    else:
+        main = native.code_object_path(gen.key)   # a main build that holds four waves per SIMD
+        main.write_bytes(b"")
+        main.with_suffix(".occ").write_text("4")
+        with pytest.warns(UserWarning, match=f"{native._BY_KEY[variant].label} build of"):
+            assert native.compile_model(gen, variant=variant) is None
+    out = native.code_object_path(gen.key, variant)
+    assert out.name.endswith((f"_{variant}" if variant else "") + f"_{native.OFFLOAD_ARCH}.hsaco")
+    assert cmds == [["hipcc-under-test", "--genco", f"--offload-arch={native.OFFLOAD_ARCH}", "-O3", "-std=c++17",
+                     f"-I{native.INCLUDE}", f"-I{native.CSRC}", *defines, str(out.with_suffix(".hip")), "-o",
+                     str(out.with_suffix(".tmp")), "-Rpass-analysis=kernel-resource-usage"]]
+    assert not out.with_suffix(".nofit").exists()   # a transient failure leaves no marker
+
+
+def test_code_object_key_is_made_of_the_same_four_files():
+    """The code objects' names carry the hash of the kernel source and the three headers it
+    includes -- not of csrc/mpcx_builds.h, which is host code."""
+    import hashlib
+
+    h = hashlib.sha1()
+    for p in (native.CSRC / "mpcx_ipm.hip", native.CSRC / "mpcx_internal.h", native.CSRC / "mpcx_net_mfma.h",
+              native.INCLUDE / "mpcx.h"):
+        h.update(p.read_bytes())
+    assert native._kernel_deps_hash() == h.hexdigest()[:10]
+    for p in (native.CSRC / "mpcx_ipm.hip", native.CSRC / "mpcx_internal.h", native.CSRC / "mpcx_net_mfma.h",
+              native.INCLUDE / "mpcx.h"):
+        assert "mpcx_builds.h" not in p.read_text()
+    assert '#include "mpcx_builds.h"' in (native.CSRC / "mpcx_runtime.cpp").read_text()
