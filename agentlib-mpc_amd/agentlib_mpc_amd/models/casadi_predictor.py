@@ -86,10 +86,12 @@ class CasadiANN:
 
     # -- symbolic ----------------------------------------------------------------
     def predict(self, inputs: Sequence) -> List[sx.Expr]:
-        """Outputs as expressions of ``inputs``.  A normalisation + one smooth hidden
-        layer + linear output network (the reference trainer's topology) becomes one
-        opaque network node per output (:func:`symbolic.ann_call`, normalisation
-        folded into the first layer); anything else is expanded layer by layer."""
+        """Outputs as expressions of ``inputs``.  A normalisation + one or two smooth hidden
+        layers + linear output network (the reference trainer's topologies; two layers up to
+        ``symbolic.DEEP_MAX_WIDTH`` units each, activations may differ) becomes one opaque
+        network node per output (:func:`symbolic.ann_call`, normalisation folded into the
+        first layer); anything else (relu, more hidden layers, a non-linear output layer,
+        normalisation between Dense layers) is expanded layer by layer."""
         x = [sx.as_expr(v) for v in inputs]
         nets = self._networks()
         if nets is not None:
@@ -112,16 +114,22 @@ class CasadiANN:
                 mean, var = spec["weights"][0].reshape(-1), spec["weights"][1].reshape(-1)
                 s_, t_ = 1.0 / np.sqrt(var), -mean / np.sqrt(var)
             scale, shift = scale * s_, shift * s_ + t_
-        if len(specs) != 2 or any(s["class_name"] != "Dense" for s in specs):
+        if len(specs) not in (2, 3) or any(s["class_name"] != "Dense" for s in specs):
             return None
-        act1 = _activation_name(specs[0]["config"].get("activation", "linear"))
-        act2 = _activation_name(specs[1]["config"].get("activation", "linear"))
-        if act1 not in sx._ACTS or act2 != "linear":
+        acts = [_activation_name(s["config"].get("activation", "linear")) for s in specs]
+        if any(a not in sx._ACTS for a in acts[:-1]) or acts[-1] != "linear":
             return None
         W1, b1 = specs[0]["weights"][0], _bias(specs[0])
         W2, b2 = specs[1]["weights"][0], _bias(specs[1])
         W1f = scale[:, None] * W1
         b1f = b1 + shift @ W1
+        if len(specs) == 3:
+            if max(W2.shape) > sx.DEEP_MAX_WIDTH:
+                return None
+            W3, b3 = specs[2]["weights"][0], _bias(specs[2])
+            return [sx.register_network(sx.DeepNetwork(W1f, b1f, W2, b2, W3[:, o], b3[o], acts[0], acts[1]))
+                    for o in range(W3.shape[1])]
+        act1 = acts[0]
         return [sx.register_network(sx.Network(W1f, b1f, W2[:, o], b2[o], act1)) for o in range(W2.shape[1])]
 
     @staticmethod

@@ -159,8 +159,9 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
     """Device code of the network evaluations on the FP64 matrix cores (empty when the
     stage has no network node): ``gen_stage_netin`` (one lane per stage writes the inputs
     of every call site to LDS), ``gen_net_{fg,gj,hess}`` (the wave evaluates each network
-    over all stages x call sites, ``mpcx_net::eval`` or, for an RBF network,
-    ``mpcx_net::eval_rbf``, csrc/mpcx_net_mfma.h) and the stage
+    over all stages x call sites, ``mpcx_net::eval``, for an RBF network
+    ``mpcx_net::eval_rbf``, for a two-hidden-layer network ``mpcx_net::eval2``,
+    csrc/mpcx_net_mfma.h) and the stage
     functions ``gen_stage_{fg,gj,hess}_m`` that read the network entries from LDS instead
     of looping over the hidden units.  Returns (lines, defines, X doubles, output doubles)."""
     sites = {}
@@ -224,7 +225,11 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
                 p2 = ", ".join(f"{a}, {b}" for a, b in L["d2"])
                 lines.append(f"__constant__ int ANN{nid}_P2{kind}[{2 * len(L['d2'])}] = {{{p2}}};")
             elif L["d2"]:
-                pw = [net.W1[a, j] * net.W1[b, j] for a, b in L["d2"] for j in range(net.H)]
+                if isinstance(net, sx.DeepNetwork):
+                    # second Hessian term: the Jacobian columns of each pair, by index
+                    p2 = ", ".join(f"{a}, {b}" for a, b in L["d2"])
+                    lines.append(f"__constant__ int ANN{nid}_P2{kind}[{2 * len(L['d2'])}] = {{{p2}}};")
+                pw = [net.W1[a, j] * net.W1[b, j] for a, b in L["d2"] for j in range(net.W1.shape[1])]
                 lines.append(f"__constant__ double ANN{nid}_PW{kind}[{len(pw)}] = "
                              f"{{{', '.join(sx._c_literal(float(v)) for v in pw)}}};")
     sig = "const double* __restrict__ L, const double* __restrict__ PS, const double* __restrict__ PG, const double TK"
@@ -251,6 +256,14 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
                              f"ANN{nid}_A, ANN{nid}_S, ANN{nid}_SH, {d1}, {p2}, lane);")
                 continue
             pw = f"ANN{nid}_PW{kind}" if L["d2"] else "nullptr"
+            if isinstance(net, sx.DeepNetwork):
+                p2 = f"ANN{nid}_P2{kind}" if L["d2"] else "nullptr"
+                lines.append(f"  mpcx_net::eval2<{L['R']}, {net.n_in}, {net.H1}, {net.H2}, {sx.ACT_CODE[net.act1]}, "
+                             f"{sx.ACT_CODE[net.act2]}, {'true' if L['wv'] else 'false'}, {len(L['d1'])}, "
+                             f"{len(L['d2'])}>(X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, "
+                             f"ANN{nid}_W1T, ANN{nid}_B1, ANN{nid}_W2, ANN{nid}_B2, ANN{nid}_W3, "
+                             f"{sx._c_literal(net.b3)}, {d1}, {pw}, {p2}, lane);")
+                continue
             lines.append(f"  mpcx_net::eval<{L['R']}, {net.n_in}, {net.H}, {sx.ACT_CODE[net.act]}, "
                          f"{'true' if L['wv'] else 'false'}, {len(L['d1'])}, {len(L['d2'])}>("
                          f"X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, ANN{nid}_W1T, ANN{nid}_B1, "

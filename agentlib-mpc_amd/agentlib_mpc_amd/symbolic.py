@@ -362,9 +362,39 @@ def sum1(items: Iterable) -> Expr:
 # evaluates each network once per stage in a loop over the hidden units with
 # the weights in constant memory (only the derivative entries that are used).
 # A second interned kind, ``RBFNetwork`` (the mean of a Gaussian process), shares the
-# node names, ``register_network``, ``ann_call`` and the derivative rules.
+# node names, ``register_network``, ``ann_call`` and the derivative rules; so does the third,
+# ``DeepNetwork`` (two hidden layers).
 
 _ACTS = ("sigmoid", "tanh", "linear", "softplus", "exponential", "gaussian")
+
+#: widest hidden layer (either one) of a two-hidden-layer network that becomes a ``DeepNetwork``
+#: node; a wider one is expanded into the stage graph.  The bound is on the wave pass, which
+#: keeps one accumulator tile per 16 units of either layer in registers (at 64: 4 tiles each for
+#: act1', act1'' o u, c2 and two Jacobian columns, 160 VGPRs per lane), and on the tables
+#: (``W2`` as ``H1 x H2`` literals per network in the generated source).
+DEEP_MAX_WIDTH = 64
+
+
+def act_derivs(act: str, a):
+    """act(a), act'(a), act''(a) (numpy)."""
+    if act == "sigmoid":
+        s = 1.0 / (1.0 + np.exp(-a))
+        s1 = s * (1.0 - s)
+        return s, s1, s1 * (1.0 - 2.0 * s)
+    if act == "tanh":
+        t = np.tanh(a)
+        t1 = 1.0 - t * t
+        return t, t1, -2.0 * t * t1
+    if act == "linear":
+        return a, np.ones_like(a), np.zeros_like(a)
+    if act == "softplus":
+        s = 1.0 / (1.0 + np.exp(-a))
+        return np.log(1.0 + np.exp(a)), s, s * (1.0 - s)
+    if act == "exponential":
+        e = np.exp(a)
+        return e, e, e
+    g = np.exp(-a * a)  # gaussian
+    return g, -2.0 * a * g, (4.0 * a * a - 2.0) * g
 
 
 class Network:
@@ -385,24 +415,7 @@ class Network:
 
     def act_derivs(self, a):
         """act(a), act'(a), act''(a) (numpy)."""
-        if self.act == "sigmoid":
-            s = 1.0 / (1.0 + np.exp(-a))
-            s1 = s * (1.0 - s)
-            return s, s1, s1 * (1.0 - 2.0 * s)
-        if self.act == "tanh":
-            t = np.tanh(a)
-            t1 = 1.0 - t * t
-            return t, t1, -2.0 * t * t1
-        if self.act == "linear":
-            return a, np.ones_like(a), np.zeros_like(a)
-        if self.act == "softplus":
-            s = 1.0 / (1.0 + np.exp(-a))
-            return np.log(1.0 + np.exp(a)), s, s * (1.0 - s)
-        if self.act == "exponential":
-            e = np.exp(a)
-            return e, e, e
-        g = np.exp(-a * a)  # gaussian
-        return g, -2.0 * a * g, (4.0 * a * a - 2.0) * g
+        return act_derivs(self.act, a)
 
     def evaluate(self, x: np.ndarray):
         """value [...], gradient [..., n_in], Hessian [..., n_in, n_in] on rows x [..., n_in]."""
@@ -451,6 +464,66 @@ class RBFNetwork:
         h = (zi * zk * S0[..., None, None] - zi * S1[..., None, :] - zk * S1[..., :, None] + S2
              - np.eye(self.n_in) * S0[..., None, None]) * (self.s[:, None] * self.s[None, :])
         return S0, g, h
+
+
+class DeepNetwork:
+    """Dense weights of a two-hidden-layer, single-output network: the third network kind.
+
+    ``y(x) = b3 + w3 . act2(W2^T act1(W1^T x + b1) + b2)``.  With ``c1 = w3 o act2'``,
+    ``c2 = w3 o act2''`` and ``u = W2 c1`` the gradient and the first Hessian term have the
+    shape of :class:`Network`'s (``w2 o act'`` -> ``act1' o u``, ``w2 o act''`` -> ``act1'' o u``);
+    the second Hessian term is ``sum_j c2_j J[j,a] J[j,b]`` with the Jacobian of the second
+    pre-activation ``J[:,i] = W2^T (act1' o W1[i,:])`` (csrc/mpcx_net_mfma.h, ``eval2``)."""
+
+    def __init__(self, W1: np.ndarray, b1: np.ndarray, W2: np.ndarray, b2: np.ndarray, w3: np.ndarray,
+                 b3: float, act1: str, act2: str):
+        for act in (act1, act2):
+            if act not in _ACTS:
+                raise ValueError(f"activation {act!r} has no smooth closed-form derivatives")
+        self.W1 = np.ascontiguousarray(W1, dtype=float)   # [n_in, H1]
+        self.b1 = np.asarray(b1, dtype=float).reshape(-1)
+        self.W2 = np.ascontiguousarray(W2, dtype=float)   # [H1, H2]
+        self.b2 = np.asarray(b2, dtype=float).reshape(-1)
+        self.w3 = np.asarray(w3, dtype=float).reshape(-1)
+        self.b3 = float(b3)
+        self.act1, self.act2 = act1, act2
+        self.n_in, self.H1 = self.W1.shape
+        self.H2 = self.W2.shape[1]
+        if self.W2.shape[0] != self.H1 or self.b1.shape[0] != self.H1 or self.b2.shape[0] != self.H2 \
+                or self.w3.shape[0] != self.H2:
+            raise ValueError("layer shapes of a two-hidden-layer network do not chain")
+        self.H = self.H1 + self.H2   # hidden units per evaluation (flop_count prices the layers itself)
+
+    def key(self) -> tuple:
+        return ("deep", self.act1, self.act2, self.b3, self.W1.shape, self.W2.shape, self.W1.tobytes(),
+                self.b1.tobytes(), self.W2.tobytes(), self.b2.tobytes(), self.w3.tobytes())
+
+    def flops(self, used) -> int:
+        """Operations of one evaluation producing the member keys ``used`` ('v', 'd<i>', 'dd<i><k>')."""
+        n_d = sum(1 for m in used if m.startswith("d") and not m.startswith("dd"))
+        n_dd = sum(1 for m in used if m.startswith("dd"))
+        f = self.H1 * (2 * self.n_in + 14) + self.H2 * (2 * self.H1 + 14 + 2)
+        if n_d or n_dd:
+            f += 2 * self.H1 * self.H2 + 2 * self.H1          # u = W2 c1, act1' o u, act1'' o u
+            f += 2 * self.H1 * n_d + 3 * self.H1 * n_dd       # one FMA per unit and entry
+        if n_dd:
+            # one Jacobian column per pair (the other one stays resident) and the contraction
+            f += n_dd * (2 * self.H1 * self.H2 + self.H1 + 3 * self.H2)
+        return f
+
+    def evaluate(self, x: np.ndarray):
+        """value [...], gradient [..., n_in], Hessian [..., n_in, n_in] on rows x [..., n_in]."""
+        x = np.asarray(x, dtype=float)
+        s0, s1, s2 = act_derivs(self.act1, x @ self.W1 + self.b1)
+        t0, t1, t2 = act_derivs(self.act2, s0 @ self.W2 + self.b2)
+        v = t0 @ self.w3 + self.b3
+        c1, c2 = t1 * self.w3, t2 * self.w3
+        u = c1 @ self.W2.T                                                  # [..., H1]
+        g = (s1 * u) @ self.W1.T
+        J = np.einsum("...k,ik,kj->...ji", s1, self.W1, self.W2)            # [..., H2, n_in]
+        h = (np.einsum("...k,ik,lk->...il", s2 * u, self.W1, self.W1)
+             + np.einsum("...j,...ji,...jl->...il", c2, J, J))
+        return v, g, h
 
 
 _NETWORKS: List[Network] = []
@@ -784,6 +857,9 @@ def flop_count(outputs: Sequence[Expr]) -> int:
     ann_flops = 0
     for (nid, _), used in groups.items():
         net = _NETWORKS[nid]
+        if isinstance(net, DeepNetwork):
+            ann_flops += net.flops(used)
+            continue
         # pre-activation + activation (+ derivatives) + one FMA per used output entry
         ann_flops += net.H * (2 * net.n_in + 14 + 2 * len(used))
     c = {k: v for k, v in count_ops(outputs).items() if not k.startswith("ann")}
@@ -931,6 +1007,8 @@ def _emit_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
     net = _NETWORKS[nid]
     if isinstance(net, RBFNetwork):
         return _emit_rbf_network(nid, x, members, gp, names, indent)
+    if isinstance(net, DeepNetwork):
+        return _emit_deep_network(nid, x, members, gp, names, indent)
     T = f"ANN{nid}"
     nin, H = net.n_in, net.H
     d1 = sorted(i for (k, i, _) in members if k == "d")
@@ -998,8 +1076,88 @@ def _emit_rbf_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: st
     return [indent + l for l in L]
 
 
+def _emit_deep_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
+                       names: Dict[int, str], indent: str) -> List[str]:
+    """Loops over the units of the two hidden layers of a :class:`DeepNetwork` on one lane:
+    forward pass, ``u = W2 c1`` when a derivative is used, one Jacobian column ``J[:, i]`` per
+    input that occurs in a used pair; only the used entries."""
+    net = _NETWORKS[nid]
+    T = f"ANN{nid}"
+    nin, H1, H2 = net.n_in, net.H1, net.H2
+    d1 = sorted(i for (k, i, _) in members if k == "d")
+    d2 = sorted((i, j) for (k, i, j) in members if k == "dd")
+    need_v = ("v", -1, -1) in members
+    a1, a2 = _ACT_C[net.act1], _ACT_C[net.act2]
+    L = [f"double {gp}s0[{H1}];"]
+    if d1 or d2:
+        L.append(f"double {gp}s1[{H1}];")
+    if d2:
+        L.append(f"double {gp}s2[{H1}];")
+    L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+    pre = " + ".join([f"{T}_B1[j]"] + [f"({x[i]}) * {T}_W1T[j * {nin} + {i}]" for i in range(nin)
+                                        if np.any(net.W1[i] != 0.0)])
+    L.append(f"  const double a = {pre};")
+    L.append("  " + a1[0])
+    L.append(f"  {gp}s0[j] = s0;")
+    if d1 or d2:
+        L += ["  " + a1[1], f"  {gp}s1[j] = s1;"]
+    if d2:
+        L += ["  " + a1[2], f"  {gp}s2[j] = s2;"]
+    L.append("}")
+    if need_v:
+        L.append(f"double {gp}v = {_c_literal(net.b3)};")
+    if d1 or d2:
+        L.append(f"double {gp}c1[{H2}];")
+    if d2:
+        L.append(f"double {gp}c2[{H2}];")
+    L.append(f"for (int k = 0; k < {H2}; ++k) {{")
+    L.append(f"  double a = {T}_B2[k];")
+    L.append(f"  for (int j = 0; j < {H1}; ++j) a += {gp}s0[j] * {T}_W2[j * {H2} + k];")
+    L.append(f"  const double w = {T}_W3[k];")
+    L.append("  " + a2[0])
+    if need_v:
+        L.append(f"  {gp}v += w * s0;")
+    if d1 or d2:
+        L += ["  " + a2[1], f"  {gp}c1[k] = w * s1;"]
+    if d2:
+        L += ["  " + a2[2], f"  {gp}c2[k] = w * s2;"]
+    L.append("}")
+    if d1 or d2:
+        L.append(f"double {gp}u[{H1}];")
+        L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+        L.append("  double u = 0.0;")
+        L.append(f"  for (int k = 0; k < {H2}; ++k) u += {T}_W2[j * {H2} + k] * {gp}c1[k];")
+        L.append(f"  {gp}u[j] = u;")
+        L.append("}")
+    L += [f"double {gp}g{i} = 0.0;" for i in d1]
+    L += [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
+    if d1 or d2:
+        L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+        if d1:
+            L.append(f"  const double e1 = {gp}s1[j] * {gp}u[j];")
+            L += [f"  {gp}g{i} += e1 * {T}_W1T[j * {nin} + {i}];" for i in d1]
+        if d2:
+            L.append(f"  const double e2 = {gp}s2[j] * {gp}u[j];")
+            L += [f"  {gp}h{i}_{j} += e2 * ({T}_W1T[j * {nin} + {i}] * {T}_W1T[j * {nin} + {j}]);" for i, j in d2]
+        L.append("}")
+    if d2:
+        cols = sorted({i for p in d2 for i in p})
+        L.append(f"for (int k = 0; k < {H2}; ++k) {{")
+        L += [f"  double J{i} = 0.0;" for i in cols]
+        L.append(f"  for (int j = 0; j < {H1}; ++j) {{")
+        L.append(f"    const double w = {T}_W2[j * {H2} + k] * {gp}s1[j];")
+        L += [f"    J{i} += w * {T}_W1T[j * {nin} + {i}];" for i in cols]
+        L.append("  }")
+        L += [f"  {gp}h{i}_{j} += {gp}c2[k] * (J{i} * J{j});" for i, j in d2]
+        L.append("}")
+    for (k, i, j), node in members.items():
+        names[node.uid] = f"{gp}v" if k == "v" else (f"{gp}g{i}" if k == "d" else f"{gp}h{i}_{j}")
+    return [indent + l for l in L]
+
+
 def network_tables(net_ids) -> List[str]:
-    """``__constant__`` weight tables of the networks (W1 transposed: [H][n_in]; an RBF
+    """``__constant__`` weight tables of the networks (W1 transposed: [H][n_in]; a two-hidden-layer
+    network adds ``W2 [H1][H2]`` in that one orientation, ``B2`` and ``W3``; an RBF
     network: the training points ``T [NT][n_in]``, the coefficients ``A [NT]``, and for the wave
     pass ``TT [NT] = -1/2 |T_j|^2`` and the input map ``S``, ``SH`` [n_in])."""
     out = []
@@ -1012,6 +1170,14 @@ def network_tables(net_ids) -> List[str]:
                     f"__constant__ double ANN{nid}_TT[{net.NT}] = {{{lit(net.tt)}}};",
                     f"__constant__ double ANN{nid}_S[{net.n_in}] = {{{lit(net.s)}}};",
                     f"__constant__ double ANN{nid}_SH[{net.n_in}] = {{{lit(net.t)}}};"]
+            continue
+        if isinstance(net, DeepNetwork):
+            lit = lambda v: ", ".join(_c_literal(float(u)) for u in np.asarray(v).reshape(-1))
+            out += [f"__constant__ double ANN{nid}_W1T[{net.H1 * net.n_in}] = {{{lit(net.W1.T)}}};",
+                    f"__constant__ double ANN{nid}_B1[{net.H1}] = {{{lit(net.b1)}}};",
+                    f"__constant__ double ANN{nid}_W2[{net.H1 * net.H2}] = {{{lit(net.W2)}}};",
+                    f"__constant__ double ANN{nid}_B2[{net.H2}] = {{{lit(net.b2)}}};",
+                    f"__constant__ double ANN{nid}_W3[{net.H2}] = {{{lit(net.w3)}}};"]
             continue
         w1t = ", ".join(_c_literal(v) for v in net.W1.T.reshape(-1))
         b1 = ", ".join(_c_literal(v) for v in net.b1)

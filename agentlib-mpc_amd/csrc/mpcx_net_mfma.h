@@ -20,7 +20,8 @@
 // hidden units 4r .. 4r + 3 of the two derivative products: no LDS round trip and no
 // lane movement between the three products.
 //
-// eval_rbf below is the same pass for the second network kind (Gaussian-process means).
+// eval_rbf below is the same pass for the second network kind (Gaussian-process means), eval2
+// for the third (two hidden layers).
 //
 // f64 MFMA lane maps (CDNA4): A[m = l & 15][k = l >> 4], B[k = l >> 4][n = l & 15],
 // D lane l register r: [m = (l >> 4) + 4 r][n = l & 15].
@@ -298,6 +299,231 @@ __device__ __forceinline__ void eval_rbf(const ldsd* X, ldsd* V, ldsd* Gd, ldsd*
           Hd[row * ND2 + o] = S[a] * S[b] * m;
         }
       }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Two hidden layers (symbolic.DeepNetwork): R evaluations of
+//
+//   y(x) = b3 + w3 . act2(a2),   a2 = W2^T act1(a1) + b2,   a1 = W1^T x + b1
+//
+// Replaces the layer-by-layer expansion of a Dense -> Dense -> Dense(linear) model of the
+// reference's trainer (ml_model_trainer.py:592-626) into the stage graph.  With
+// c1 = w3 o act2'(a2), c2 = w3 o act2''(a2) and u = W2 c1:
+//
+//   dy/dx_i       = sum_k W1[i,k] act1'(a1_k) u_k
+//   d2y/dx_a dx_b = sum_k W1[a,k] W1[b,k] act1''(a1_k) u_k + sum_j c2_j J[j,a] J[j,b],
+//   J[:,i] = W2^T (act1'(a1) o W1[i,:])
+//
+// Layout.  The layer-1 accumulator is eval's (hidden-1 unit 4r + (l >> 4) of the tile in
+// register r, evaluation l & 15 on the lane): after act1 it is the B operand of a k-step over
+// hidden-1 units, so a2^T = W2^T s1 (A operand W2 read as [k = hidden-1][m = hidden-2]) lands in
+// the same layout over the hidden-2 units.  c1 there is the B operand of a k-step over
+// hidden-2 units, and u^T = W2 c1 (A operand W2 read as [m = hidden-1][k = hidden-2]: the same
+// table with the two strides exchanged) lands in the layer-1 layout again, where act1' and
+// act1'' sit.  The gradient and the first Hessian term are then eval's products on act1' o u
+// and act1'' o u.  A Jacobian column J[:,i] is one more product of the first kind with the B
+// operand act1' o W1[i,:].
+//
+// Second Hessian term.  The pairs are walked in table order (sorted: equal first index a
+// adjacent).  J[:,a] stays in registers while a repeats; J[:,b] is recomputed per pair unless
+// b = a: about half the products of forming both columns for every pair, and two resident
+// columns instead of one per input.  The contraction over the hidden-2 units is a sum over the
+// lane's registers and the four lanes of the evaluation; the result is added to the register
+// of the first term's accumulator tile that holds the pair, so Hd is written once.
+//
+// Pad rows: act(0) != 0 for four of the activations, so a padded hidden-1 unit meets a zero W2
+// operand in every product that sums over it (and gives u = 0), a padded hidden-2 unit a zero
+// w3 (c1 = c2 = 0) and a zero W2 operand; rows of the last tile past R write nothing.
+//
+// X[R][NIN] (LDS) -> V[R] (if WV), Gd[R][ND1] (inputs D1[]), Hd[R][ND2] (pairs P2[ND2][2], table
+// PW[ND2][H1] of W1[a,k] W1[b,k]).  W1T[H1][NIN], B1[H1], W2[H1][H2], B2[H2], W3[H2].  No LDS
+// besides X and the outputs.
+template <int R, int NIN, int H1, int H2, int ACT1, int ACT2, bool WV, int ND1, int ND2>
+__device__ __forceinline__ void eval2(const ldsd* X, ldsd* V, ldsd* Gd, ldsd* Hd, const double* W1T,
+                                      const double* B1, const double* W2, const double* B2,
+                                      const double* W3, double b3, const int* D1, const double* PW,
+                                      const int* P2, int lane) {
+  constexpr int JT = (H1 + 15) / 16;   // hidden-1 tiles
+  constexpr int KT = (H2 + 15) / 16;   // hidden-2 tiles
+  constexpr int KS = (NIN + 3) / 4;    // k-steps over the inputs
+  constexpr bool W1D = ND1 > 0, W2D = ND2 > 0;
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll 1
+  for (int rt = 0; rt < (R + 15) / 16; ++rt) {
+    const int row = rt * 16 + lr;
+    // layer 1: as eval
+    d4 acc[JT];
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = jt * 16 + lk + 4 * r;
+        acc[jt][r] = j < H1 ? B1[j] : 0.0;
+      }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int i = ks * 4 + lk;
+      const double bx = (row < R && i < NIN) ? X[row * NIN + i] : 0.0;
+#pragma unroll
+      for (int jt = 0; jt < JT; ++jt) {
+        const int jj = jt * 16 + lr;
+        const double aw = (jj < H1 && i < NIN) ? W1T[jj * NIN + i] : 0.0;
+        acc[jt] = mfma(aw, bx, acc[jt]);
+      }
+    }
+    double s0[JT][4], s1[JT][4], s2[JT][4];
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) act<ACT1>(acc[jt][r], s0[jt][r], s1[jt][r], s2[jt][r]);
+    // layer 2: a2^T = W2^T s0 + b2, hidden-2 unit on the accumulator row
+    d4 acc2[KT];
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int k = kt * 16 + lk + 4 * r;
+        acc2[kt][r] = k < H2 ? B2[k] : 0.0;
+      }
+      const int kk = kt * 16 + lr;
+#pragma unroll
+      for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int j = jt * 16 + 4 * r + lk;
+          const double aw = (j < H1 && kk < H2) ? W2[j * H2 + kk] : 0.0;
+          acc2[kt] = mfma(aw, s0[jt][r], acc2[kt]);
+        }
+    }
+    double c1[KT][4], c2[KT][4];
+    double v = 0.0;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int k = kt * 16 + lk + 4 * r;
+        const double w = k < H2 ? W3[k] : 0.0;
+        double t0, t1, t2;
+        act<ACT2>(acc2[kt][r], t0, t1, t2);
+        v += w * t0; c1[kt][r] = w * t1; c2[kt][r] = w * t2;
+      }
+    if constexpr (WV) {
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (lk == 0 && row < R) V[row] = v + b3;
+    }
+    if constexpr (W1D || W2D) {
+      // u^T = W2 c1 in the layer-1 layout; e1 = act1' o u, e2 = act1'' o u
+      double e1[JT][4], e2[JT][4];
+#pragma unroll
+      for (int jt = 0; jt < JT; ++jt) {
+        const int jj = jt * 16 + lr;
+        d4 u = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = kt * 16 + 4 * r + lk;
+            const double aw = (jj < H1 && k < H2) ? W2[jj * H2 + k] : 0.0;
+            u = mfma(aw, c1[kt][r], u);
+          }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          e1[jt][r] = s1[jt][r] * u[r];
+          e2[jt][r] = s2[jt][r] * u[r];
+        }
+      }
+      if constexpr (W1D) {
+#pragma unroll
+        for (int it = 0; it < (ND1 + 15) / 16; ++it) {
+          const int ii = it * 16 + lr;
+          const int col = ii < ND1 ? D1[ii] : 0;
+          d4 g = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j = jt * 16 + 4 * r + lk;
+              const double aw = (ii < ND1 && j < H1) ? W1T[j * NIN + col] : 0.0;
+              g = mfma(aw, e1[jt][r], g);
+            }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = it * 16 + lk + 4 * r;
+            if (o < ND1 && row < R) Gd[row * ND1 + o] = g[r];
+          }
+        }
+      }
+      if constexpr (W2D) {
+        // J[:, i] in the layer-2 layout
+        auto jcol = [&](const int i, d4 (&J)[KT]) __attribute__((always_inline)) {
+          double b[JT][4];
+#pragma unroll
+          for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j = jt * 16 + lk + 4 * r;
+              b[jt][r] = s1[jt][r] * (j < H1 ? W1T[j * NIN + i] : 0.0);
+            }
+#pragma unroll
+          for (int kt = 0; kt < KT; ++kt) {
+            const int kk = kt * 16 + lr;
+            J[kt] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int j = jt * 16 + 4 * r + lk;
+                const double aw = (j < H1 && kk < H2) ? W2[j * H2 + kk] : 0.0;
+                J[kt] = mfma(aw, b[jt][r], J[kt]);
+              }
+          }
+        };
+        d4 Ja[KT], Jb[KT];
+        int ca = -1;   // input of the resident column
+#pragma unroll 1
+        for (int pt = 0; pt < (ND2 + 15) / 16; ++pt) {
+          d4 h = {0.0, 0.0, 0.0, 0.0};
+          const int pend = (pt * 16 + 16 < ND2) ? pt * 16 + 16 : ND2;
+#pragma unroll 1
+          for (int p = pt * 16; p < pend; ++p) {
+            const int a = P2[2 * p], b = P2[2 * p + 1];
+            if (a != ca) {
+              jcol(a, Ja);
+              ca = a;
+            }
+            if (b != a) jcol(b, Jb);
+            double t = 0.0;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                t += c2[kt][r] * Ja[kt][r] * (b != a ? Jb[kt][r] : Ja[kt][r]);
+            t += __shfl_xor(t, 16, 64);
+            t += __shfl_xor(t, 32, 64);
+            // pair p is row p - 16 pt of the tile: register (p >> 2) & 3 of lane quarter p & 3
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              h[r] += (lk == (p & 3) && r == ((p >> 2) & 3)) ? t : 0.0;
+          }
+          const int pp = pt * 16 + lr;
+#pragma unroll
+          for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int j = jt * 16 + 4 * r + lk;
+              const double aw = (pp < ND2 && j < H1) ? PW[pp * H1 + j] : 0.0;
+              h = mfma(aw, e2[jt][r], h);
+            }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = pt * 16 + lk + 4 * r;
+            if (o < ND2 && row < R) Hd[row * ND2 + o] = h[r];
+          }
+        }
+      }
+    }
   }
 }
 
