@@ -147,22 +147,16 @@ def factorisation_plan(nlp: StageNLP):
     return [], True
 
 
-#: most training points of an RBF network (GPR model) the generator accepts.  The wave pass
-#: streams the points, so registers and LDS do not grow with them; the bound is on the tables
-#: (T, TT, A as literals in the generated source and lane-indexed reads in the kernel): at 512
-#: points and the 18 inputs of the widest tested network they are 80 KB per network, which two
-#: networks per stage keep resident in L2, and the generated source stays below 2 MB.
-RBF_MAX_POINTS = 512
+#: most training points of an RBF network (GPR model) the generator accepts
+RBF_MAX_POINTS = sx.RBFNetwork.MAX_POINTS
 
 
 def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emit_h, to_compact):
     """Device code of the network evaluations on the FP64 matrix cores (empty when the
     stage has no network node): ``gen_stage_netin`` (one lane per stage writes the inputs
     of every call site to LDS), ``gen_net_{fg,gj,hess}`` (the wave evaluates each network
-    over all stages x call sites, ``mpcx_net::eval``, for an RBF network
-    ``mpcx_net::eval_rbf``, for a two-hidden-layer network ``mpcx_net::eval2``,
-    csrc/mpcx_net_mfma.h) and the stage
-    functions ``gen_stage_{fg,gj,hess}_m`` that read the network entries from LDS instead
+    over all stages x call sites by the call its kind's ``wave_call`` writes: ``mpcx_net::eval``,
+    ``eval_rbf`` or ``eval2``, csrc/mpcx_net_mfma.h) and the stage functions ``gen_stage_{fg,gj,hess}_m`` that read the network entries from LDS instead
     of looping over the hidden units.  Returns (lines, defines, X doubles, output doubles)."""
     sites = {}
     for outs in (fg_assign, gj_all, h_all):
@@ -179,10 +173,7 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
     for nid, keys in nets.items():
         xoff[nid] = netx
         netx += N * len(keys) * sx.network(nid).n_in
-        net = sx.network(nid)
-        if isinstance(net, sx.RBFNetwork) and net.NT > RBF_MAX_POINTS:
-            raise ValueError(f"GPR model with {net.NT} training points: the MI355X backend takes at most "
-                             f"{RBF_MAX_POINTS} (codegen.RBF_MAX_POINTS)")
+        sx.network(nid).check_wave()
 
     def layout(outs):
         mem = {nid: set() for nid in nets}
@@ -217,21 +208,8 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
     lines: List[str] = ['#include "mpcx_net_mfma.h"']
     for kind, (lay, _) in kinds.items():
         for nid, L in lay.items():
-            net = sx.network(nid)
-            if L["d1"]:
-                lines.append(f"__constant__ int ANN{nid}_D1{kind}[{len(L['d1'])}] = {{{', '.join(map(str, L['d1']))}}};")
-            if L["d2"] and isinstance(net, sx.RBFNetwork):
-                # the pair operand T_ja T_jb is formed from two reads of T: only the index pairs
-                p2 = ", ".join(f"{a}, {b}" for a, b in L["d2"])
-                lines.append(f"__constant__ int ANN{nid}_P2{kind}[{2 * len(L['d2'])}] = {{{p2}}};")
-            elif L["d2"]:
-                if isinstance(net, sx.DeepNetwork):
-                    # second Hessian term: the Jacobian columns of each pair, by index
-                    p2 = ", ".join(f"{a}, {b}" for a, b in L["d2"])
-                    lines.append(f"__constant__ int ANN{nid}_P2{kind}[{2 * len(L['d2'])}] = {{{p2}}};")
-                pw = [net.W1[a, j] * net.W1[b, j] for a, b in L["d2"] for j in range(net.W1.shape[1])]
-                lines.append(f"__constant__ double ANN{nid}_PW{kind}[{len(pw)}] = "
-                             f"{{{', '.join(sx._c_literal(float(v)) for v in pw)}}};")
+            tables = [("D1", L["d1"])] + (sx.network(nid).wave_tables(L["d2"]) if L["d2"] else [])
+            lines += [sx._c_table(f"ANN{nid}_{suffix}{kind}", t) for suffix, t in tables if len(t)]
     sig = "const double* __restrict__ L, const double* __restrict__ PS, const double* __restrict__ PG, const double TK"
     xa = []
     for (nid, key), (_, args, _) in sites.items():
@@ -244,30 +222,10 @@ def _network_section(nlp: StageNLP, bind, fg_assign, gj_all, h_all, emit_gj, emi
         lines.append(f"__device__ __forceinline__ void gen_net_{kind}(const mpcx_elim_ld* X, mpcx_elim_ld* O, "
                      f"const int lane) {{")
         for nid, L in lay.items():
-            if not (L["wv"] or L["d1"] or L["d2"]):
-                continue
-            net = sx.network(nid)
-            d1 = f"ANN{nid}_D1{kind}" if L["d1"] else "nullptr"
-            if isinstance(net, sx.RBFNetwork):
-                p2 = f"ANN{nid}_P2{kind}" if L["d2"] else "nullptr"
-                lines.append(f"  mpcx_net::eval_rbf<{L['R']}, {net.n_in}, {net.NT}, "
-                             f"{'true' if L['wv'] else 'false'}, {len(L['d1'])}, {len(L['d2'])}>("
-                             f"X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, ANN{nid}_T, ANN{nid}_TT, "
-                             f"ANN{nid}_A, ANN{nid}_S, ANN{nid}_SH, {d1}, {p2}, lane);")
-                continue
-            pw = f"ANN{nid}_PW{kind}" if L["d2"] else "nullptr"
-            if isinstance(net, sx.DeepNetwork):
-                p2 = f"ANN{nid}_P2{kind}" if L["d2"] else "nullptr"
-                lines.append(f"  mpcx_net::eval2<{L['R']}, {net.n_in}, {net.H1}, {net.H2}, {sx.ACT_CODE[net.act1]}, "
-                             f"{sx.ACT_CODE[net.act2]}, {'true' if L['wv'] else 'false'}, {len(L['d1'])}, "
-                             f"{len(L['d2'])}>(X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, "
-                             f"ANN{nid}_W1T, ANN{nid}_B1, ANN{nid}_W2, ANN{nid}_B2, ANN{nid}_W3, "
-                             f"{sx._c_literal(net.b3)}, {d1}, {pw}, {p2}, lane);")
-                continue
-            lines.append(f"  mpcx_net::eval<{L['R']}, {net.n_in}, {net.H}, {sx.ACT_CODE[net.act]}, "
-                         f"{'true' if L['wv'] else 'false'}, {len(L['d1'])}, {len(L['d2'])}>("
-                         f"X + {xoff[nid]}, O + {L['ov']}, O + {L['og']}, O + {L['oh']}, ANN{nid}_W1T, ANN{nid}_B1, "
-                         f"ANN{nid}_W2, {sx._c_literal(net.b2)}, {d1}, {pw}, lane);")
+            if L["wv"] or L["d1"] or L["d2"]:
+                io = [f"X + {xoff[nid]}", f"O + {L['ov']}", f"O + {L['og']}", f"O + {L['oh']}"]
+                lines.append("  " + sx.network(nid).wave_call(f"ANN{nid}", kind, L["R"], L["wv"], len(L["d1"]),
+                                                              len(L["d2"]), io))
         lines.append("}")
     ext = "const double* __restrict__ NO, const int K"
     lines += [f"__device__ __forceinline__ void gen_stage_fg_m({sig}, double* __restrict__ f, double* __restrict__ g, "

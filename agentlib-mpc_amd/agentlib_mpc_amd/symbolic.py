@@ -367,6 +367,9 @@ def sum1(items: Iterable) -> Expr:
 
 _ACTS = ("sigmoid", "tanh", "linear", "softplus", "exponential", "gaussian")
 
+#: activation codes of the wave-level network pass (csrc/mpcx_net_mfma.h)
+ACT_CODE = {a: i for i, a in enumerate(_ACTS)}
+
 #: widest hidden layer (either one) of a two-hidden-layer network that becomes a ``DeepNetwork``
 #: node; a wider one is expanded into the stage graph.  The bound is on the wave pass, which
 #: keeps one accumulator tile per 16 units of either layer in registers (at 64: 4 tiles each for
@@ -397,8 +400,50 @@ def act_derivs(act: str, a):
     return g, -2.0 * a * g, (4.0 * a * a - 2.0) * g
 
 
-class Network:
+def _c_table(name: str, values) -> str:
+    """``__constant__`` table of C literals: ``int`` for an integer array, else ``double``."""
+    v = np.asarray(values).reshape(-1)
+    ints = v.dtype.kind in "iu"
+    body = ", ".join(str(int(u)) if ints else _c_literal(float(u)) for u in v)
+    return f"__constant__ {'int' if ints else 'double'} {name}[{v.size}] = {{{body}}};"
+
+
+def _pair_weights(W1: np.ndarray, d2) -> np.ndarray:
+    """``PW [ND2][H]``: ``W1[a, j] W1[b, j]`` per used Hessian entry (a, b)."""
+    return np.array([W1[a] * W1[b] for a, b in d2])
+
+
+class _NetworkKind:
+    """What the generators ask of a network kind, besides ``key()`` and ``evaluate(x)``:
+    ``flops(used)`` (operations of one evaluation producing the member keys ``used``), ``tables()``
+    (the constant tables ``ANN<id>_<suffix>`` as (suffix, array) pairs), ``emit_lane(...)`` (the
+    evaluation on one lane, only the used entries), and for the wave pass ``mpcx_net::<wave_fn>``
+    (csrc/mpcx_net_mfma.h): ``wave_tables(d2)`` (the tables ``ANN<id>_<suffix><kind>`` the Hessian
+    entries ``d2`` need; ``wave_pair_args``: their suffixes in argument order), ``wave_signature()``
+    (template arguments between the input count and ``WV``, table suffixes, trailing scalars) and
+    ``check_wave()`` (raises ``ValueError`` where the pass does not take the network)."""
+
+    def flops(self, used) -> int:
+        # pre-activation + activation (+ derivatives) + one FMA per used output entry
+        return self.terms * (2 * self.n_in + 14 + 2 * len(used))
+
+    def check_wave(self) -> None:
+        pass
+
+    def wave_call(self, T: str, kind: str, R: int, wv: bool, nd1: int, nd2: int, io: Sequence[str]) -> str:
+        """The call evaluating ``R`` rows (``io``: the LDS input and the three output pointers)."""
+        tab = lambda suffix, n: f"{T}_{suffix}{kind}" if n else "nullptr"
+        template, names, scalars = self.wave_signature()
+        targs = [R, self.n_in, *template, "true" if wv else "false", nd1, nd2]
+        args = [*io, *(f"{T}_{s}" for s in names), *map(_c_literal, scalars), tab("D1", nd1),
+                *(tab(s, nd2) for s in self.wave_pair_args), "lane"]
+        return f"mpcx_net::{self.wave_fn}<{', '.join(map(str, targs))}>({', '.join(args)});"
+
+
+class Network(_NetworkKind):
     """Dense weights of a single-hidden-layer, single-output network."""
+
+    wave_fn, wave_pair_args = "eval", ("PW",)
 
     def __init__(self, W1: np.ndarray, b1: np.ndarray, w2: np.ndarray, b2: float, act: str):
         if act not in _ACTS:
@@ -409,9 +454,47 @@ class Network:
         self.b2 = float(b2)
         self.act = act
         self.n_in, self.H = self.W1.shape
+        self.terms = self.H
 
     def key(self) -> tuple:
         return (self.act, self.b2, self.W1.tobytes(), self.b1.tobytes(), self.w2.tobytes())
+
+    def tables(self):
+        return [("W1T", self.W1.T), ("B1", self.b1), ("W2", self.w2)]
+
+    def wave_tables(self, d2):
+        return [("PW", _pair_weights(self.W1, d2))]
+
+    def wave_signature(self):
+        return [self.H, ACT_CODE[self.act]], ("W1T", "B1", "W2"), [self.b2]
+
+    def emit_lane(self, T, x, need_v, d1, d2, gp) -> List[str]:
+        """One loop over the hidden units computing the used value/derivative entries."""
+        nin = self.n_in
+        L = []
+        if need_v:
+            L.append(f"double {gp}v = {_c_literal(self.b2)};")
+        L += _lane_accumulators(gp, d1, d2)
+        L.append("#pragma unroll 4")
+        L.append(f"for (int j = 0; j < {self.H}; ++j) {{")
+        L.append(f"  const double a = {_lane_preactivation(T, x, self.W1)};")
+        acts = _ACT_C[self.act]
+        L.append("  " + acts[0])
+        L.append(f"  const double w = {T}_W2[j];")
+        if need_v:
+            L.append(f"  {gp}v += w * s0;")
+        if d1:
+            L.append("  " + acts[1])
+            L.append("  const double c1 = w * s1;")
+            L += [f"  {gp}g{i} += c1 * {T}_W1T[j * {nin} + {i}];" for i in d1]
+        if d2:
+            if not d1:
+                L.append("  " + acts[1])
+            L.append("  " + acts[2])
+            L.append("  const double c2 = w * s2;")
+            L += [f"  {gp}h{i}_{j} += c2 * ({T}_W1T[j * {nin} + {i}] * {T}_W1T[j * {nin} + {j}]);" for i, j in d2]
+        L.append("}")
+        return L
 
     def act_derivs(self, a):
         """act(a), act'(a), act''(a) (numpy)."""
@@ -427,7 +510,7 @@ class Network:
         return v, g, h
 
 
-class RBFNetwork:
+class RBFNetwork(_NetworkKind):
     """Mean of a Gaussian process with an RBF kernel, single output: the second network kind.
 
     ``y(x) = sum_j a_j exp(-1/2 |z - T_j|^2)`` with ``z = s o x + t``: input normalisation and
@@ -435,6 +518,13 @@ class RBFNetwork:
     (training points / length scale); ``a_j`` carries the output scale, the kernel's constant
     and the dual coefficient.  ``tt_j = -1/2 |T_j|^2`` is the table the wave pass starts its
     accumulators from (csrc/mpcx_net_mfma.h, ``eval_rbf``)."""
+
+    wave_fn, wave_pair_args = "eval_rbf", ("P2",)
+
+    #: most training points the generator accepts.  The wave pass streams the points; the bound is
+    #: on the tables (T, TT, A as literals in the source, lane-indexed reads in the kernel): 80 KB
+    #: per network at 18 inputs, L2-resident for two networks per stage, source below 2 MB.
+    MAX_POINTS = 512
 
     def __init__(self, T: np.ndarray, a: np.ndarray, s: np.ndarray, t: np.ndarray):
         self.T = np.ascontiguousarray(T, dtype=float)      # [NT, n_in]
@@ -445,10 +535,46 @@ class RBFNetwork:
         if self.a.shape[0] != self.NT:
             raise ValueError("one coefficient per training point")
         self.tt = -0.5 * np.sum(self.T * self.T, axis=1)
-        self.H = self.NT   # terms per evaluation (flop_count)
+        self.terms = self.NT
 
     def key(self) -> tuple:
         return ("rbf", self.T.shape, self.T.tobytes(), self.a.tobytes(), self.s.tobytes(), self.t.tobytes())
+
+    def tables(self):
+        return [("T", self.T), ("A", self.a), ("TT", self.tt), ("S", self.s), ("SH", self.t)]
+
+    def wave_tables(self, d2):
+        # P2 [ND2][2]: the pair operand T_ja T_jb is formed from two reads of T, only the index pairs
+        return [("P2", d2)]
+
+    def wave_signature(self):
+        return [self.NT], ("T", "TT", "A", "S", "SH"), []
+
+    def emit_lane(self, T, x, need_v, d1, d2, gp) -> List[str]:
+        """One loop over the training points with direct differences ``z_i - T_ji`` (no
+        cancellation on one lane), only the used entries."""
+        nin = self.n_in
+        L = [f"const double {gp}z{i} = ({x[i]}) * {_c_literal(self.s[i])} + {_c_literal(self.t[i])};" for i in range(nin)]
+        if need_v:
+            L.append(f"double {gp}v = 0.0;")
+        L += _lane_accumulators(gp, d1, d2)
+        L.append("#pragma unroll 4")
+        L.append(f"for (int j = 0; j < {self.NT}; ++j) {{")
+        L += [f"  const double d{i} = {gp}z{i} - {T}_T[j * {nin} + {i}];" for i in range(nin)]
+        L.append(f"  const double w = {T}_A[j] * exp(-0.5 * ({' + '.join(f'd{i} * d{i}' for i in range(nin))}));")
+        if need_v:
+            L.append(f"  {gp}v += w;")
+        L += [f"  {gp}g{i} += w * d{i};" for i in d1]
+        L += [f"  {gp}h{i}_{j} += w * (d{i} * d{j}{' - 1.0' if i == j else ''});" for i, j in d2]
+        L.append("}")
+        L += [f"{gp}g{i} *= {_c_literal(-self.s[i])};" for i in d1]
+        L += [f"{gp}h{i}_{j} *= {_c_literal(self.s[i] * self.s[j])};" for i, j in d2]
+        return L
+
+    def check_wave(self) -> None:
+        if self.NT > self.MAX_POINTS:
+            raise ValueError(f"GPR model with {self.NT} training points: the MI355X backend takes at most "
+                             f"{self.MAX_POINTS} (codegen.RBF_MAX_POINTS)")
 
     def evaluate(self, x: np.ndarray):
         """value [...], gradient [..., n_in], Hessian [..., n_in, n_in] on rows x [..., n_in]: the
@@ -466,7 +592,7 @@ class RBFNetwork:
         return S0, g, h
 
 
-class DeepNetwork:
+class DeepNetwork(_NetworkKind):
     """Dense weights of a two-hidden-layer, single-output network: the third network kind.
 
     ``y(x) = b3 + w3 . act2(W2^T act1(W1^T x + b1) + b2)``.  With ``c1 = w3 o act2'``,
@@ -474,6 +600,8 @@ class DeepNetwork:
     shape of :class:`Network`'s (``w2 o act'`` -> ``act1' o u``, ``w2 o act''`` -> ``act1'' o u``);
     the second Hessian term is ``sum_j c2_j J[j,a] J[j,b]`` with the Jacobian of the second
     pre-activation ``J[:,i] = W2^T (act1' o W1[i,:])`` (csrc/mpcx_net_mfma.h, ``eval2``)."""
+
+    wave_fn, wave_pair_args = "eval2", ("PW", "P2")
 
     def __init__(self, W1: np.ndarray, b1: np.ndarray, W2: np.ndarray, b2: np.ndarray, w3: np.ndarray,
                  b3: float, act1: str, act2: str):
@@ -492,11 +620,87 @@ class DeepNetwork:
         if self.W2.shape[0] != self.H1 or self.b1.shape[0] != self.H1 or self.b2.shape[0] != self.H2 \
                 or self.w3.shape[0] != self.H2:
             raise ValueError("layer shapes of a two-hidden-layer network do not chain")
-        self.H = self.H1 + self.H2   # hidden units per evaluation (flop_count prices the layers itself)
 
     def key(self) -> tuple:
         return ("deep", self.act1, self.act2, self.b3, self.W1.shape, self.W2.shape, self.W1.tobytes(),
                 self.b1.tobytes(), self.W2.tobytes(), self.b2.tobytes(), self.w3.tobytes())
+
+    def tables(self):
+        return [("W1T", self.W1.T), ("B1", self.b1), ("W2", self.W2), ("B2", self.b2), ("W3", self.w3)]
+
+    def wave_tables(self, d2):
+        # P2: the Jacobian columns of each pair (second Hessian term); PW: the first term
+        return [("P2", d2), ("PW", _pair_weights(self.W1, d2))]
+
+    def wave_signature(self):
+        return [self.H1, self.H2, ACT_CODE[self.act1], ACT_CODE[self.act2]], ("W1T", "B1", "W2", "B2", "W3"), [self.b3]
+
+    def emit_lane(self, T, x, need_v, d1, d2, gp) -> List[str]:
+        """Loops over the units of the two hidden layers on one lane: forward pass, ``u = W2 c1``
+        when a derivative is used, one Jacobian column ``J[:, i]`` per input that occurs in a used
+        pair; only the used entries."""
+        nin, H1, H2 = self.n_in, self.H1, self.H2
+        a1, a2 = _ACT_C[self.act1], _ACT_C[self.act2]
+        L = [f"double {gp}s0[{H1}];"]
+        if d1 or d2:
+            L.append(f"double {gp}s1[{H1}];")
+        if d2:
+            L.append(f"double {gp}s2[{H1}];")
+        L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+        L.append(f"  const double a = {_lane_preactivation(T, x, self.W1)};")
+        L.append("  " + a1[0])
+        L.append(f"  {gp}s0[j] = s0;")
+        if d1 or d2:
+            L += ["  " + a1[1], f"  {gp}s1[j] = s1;"]
+        if d2:
+            L += ["  " + a1[2], f"  {gp}s2[j] = s2;"]
+        L.append("}")
+        if need_v:
+            L.append(f"double {gp}v = {_c_literal(self.b3)};")
+        if d1 or d2:
+            L.append(f"double {gp}c1[{H2}];")
+        if d2:
+            L.append(f"double {gp}c2[{H2}];")
+        L.append(f"for (int k = 0; k < {H2}; ++k) {{")
+        L.append(f"  double a = {T}_B2[k];")
+        L.append(f"  for (int j = 0; j < {H1}; ++j) a += {gp}s0[j] * {T}_W2[j * {H2} + k];")
+        L.append(f"  const double w = {T}_W3[k];")
+        L.append("  " + a2[0])
+        if need_v:
+            L.append(f"  {gp}v += w * s0;")
+        if d1 or d2:
+            L += ["  " + a2[1], f"  {gp}c1[k] = w * s1;"]
+        if d2:
+            L += ["  " + a2[2], f"  {gp}c2[k] = w * s2;"]
+        L.append("}")
+        if d1 or d2:
+            L.append(f"double {gp}u[{H1}];")
+            L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+            L.append("  double u = 0.0;")
+            L.append(f"  for (int k = 0; k < {H2}; ++k) u += {T}_W2[j * {H2} + k] * {gp}c1[k];")
+            L.append(f"  {gp}u[j] = u;")
+            L.append("}")
+        L += _lane_accumulators(gp, d1, d2)
+        if d1 or d2:
+            L.append(f"for (int j = 0; j < {H1}; ++j) {{")
+            if d1:
+                L.append(f"  const double e1 = {gp}s1[j] * {gp}u[j];")
+                L += [f"  {gp}g{i} += e1 * {T}_W1T[j * {nin} + {i}];" for i in d1]
+            if d2:
+                L.append(f"  const double e2 = {gp}s2[j] * {gp}u[j];")
+                L += [f"  {gp}h{i}_{j} += e2 * ({T}_W1T[j * {nin} + {i}] * {T}_W1T[j * {nin} + {j}]);" for i, j in d2]
+            L.append("}")
+        if d2:
+            cols = sorted({i for p in d2 for i in p})
+            L.append(f"for (int k = 0; k < {H2}; ++k) {{")
+            L += [f"  double J{i} = 0.0;" for i in cols]
+            L.append(f"  for (int j = 0; j < {H1}; ++j) {{")
+            L.append(f"    const double w = {T}_W2[j * {H2} + k] * {gp}s1[j];")
+            L += [f"    J{i} += w * {T}_W1T[j * {nin} + {i}];" for i in cols]
+            L.append("  }")
+            L += [f"  {gp}h{i}_{j} += {gp}c2[k] * (J{i} * J{j});" for i, j in d2]
+            L.append("}")
+        return L
 
     def flops(self, used) -> int:
         """Operations of one evaluation producing the member keys ``used`` ('v', 'd<i>', 'dd<i><k>')."""
@@ -856,12 +1060,7 @@ def flop_count(outputs: Sequence[Expr]) -> int:
             groups.setdefault((pa[1], tuple(a.uid for a in n.args)), set()).add(pa[0] + str(pa[2]) + str(pa[3]))
     ann_flops = 0
     for (nid, _), used in groups.items():
-        net = _NETWORKS[nid]
-        if isinstance(net, DeepNetwork):
-            ann_flops += net.flops(used)
-            continue
-        # pre-activation + activation (+ derivatives) + one FMA per used output entry
-        ann_flops += net.H * (2 * net.n_in + 14 + 2 * len(used))
+        ann_flops += _NETWORKS[nid].flops(used)
     c = {k: v for k, v in count_ops(outputs).items() if not k.startswith("ann")}
     # transcendental functions are priced as a handful of flops
     weights = {"exp": 8, "log": 8, "sqrt": 4, "tanh": 10, "sin": 8, "cos": 8,
@@ -983,10 +1182,6 @@ def network_sites(outputs: Sequence[Expr]) -> Dict[tuple, Tuple[int, tuple, Dict
     return sites
 
 
-#: activation codes of the wave-level network pass (csrc/mpcx_net_mfma.h)
-ACT_CODE = {a: i for i, a in enumerate(_ACTS)}
-
-
 _ACT_C = {
     "sigmoid": ("const double s0 = 1.0 / (1.0 + exp(-a));", "const double s1 = s0 * (1.0 - s0);",
                 "const double s2 = s1 * (1.0 - 2.0 * s0);"),
@@ -1001,191 +1196,37 @@ _ACT_C = {
 }
 
 
+def _lane_accumulators(gp: str, d1, d2) -> List[str]:
+    return [f"double {gp}g{i} = 0.0;" for i in d1] + [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
+
+
+def _lane_preactivation(T: str, x: List[str], W1: np.ndarray) -> str:
+    """``b1_j + sum_i W1_ij x_i`` of hidden unit ``j`` (inputs with a zero row of ``W1`` left out)."""
+    nin = W1.shape[0]
+    return " + ".join([f"{T}_B1[j]"] + [f"({x[i]}) * {T}_W1T[j * {nin} + {i}]" for i in range(nin)
+                                       if np.any(W1[i] != 0.0)])
+
+
 def _emit_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
                   names: Dict[int, str], indent: str) -> List[str]:
-    """One loop over the hidden units computing the used value/derivative entries."""
-    net = _NETWORKS[nid]
-    if isinstance(net, RBFNetwork):
-        return _emit_rbf_network(nid, x, members, gp, names, indent)
-    if isinstance(net, DeepNetwork):
-        return _emit_deep_network(nid, x, members, gp, names, indent)
-    T = f"ANN{nid}"
-    nin, H = net.n_in, net.H
+    """The per-lane evaluation of one call site (the kind's ``emit_lane``): the used
+    value/derivative entries end up in ``<gp>v``, ``<gp>g<i>``, ``<gp>h<i>_<j>``."""
     d1 = sorted(i for (k, i, _) in members if k == "d")
     d2 = sorted((i, j) for (k, i, j) in members if k == "dd")
-    need_v = ("v", -1, -1) in members
-    L = []
-    if need_v:
-        L.append(f"double {gp}v = {_c_literal(net.b2)};")
-    L += [f"double {gp}g{i} = 0.0;" for i in d1]
-    L += [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
-    L.append("#pragma unroll 4")
-    L.append(f"for (int j = 0; j < {H}; ++j) {{")
-    pre = " + ".join([f"{T}_B1[j]"] + [f"({x[i]}) * {T}_W1T[j * {nin} + {i}]" for i in range(nin)
-                                        if np.any(net.W1[i] != 0.0)])
-    L.append(f"  const double a = {pre};")
-    acts = _ACT_C[net.act]
-    L.append("  " + acts[0])
-    L.append(f"  const double w = {T}_W2[j];")
-    if need_v:
-        L.append(f"  {gp}v += w * s0;")
-    if d1:
-        L.append("  " + acts[1])
-        L.append("  const double c1 = w * s1;")
-        L += [f"  {gp}g{i} += c1 * {T}_W1T[j * {nin} + {i}];" for i in d1]
-    if d2:
-        if not d1:
-            L.append("  " + acts[1])
-        L.append("  " + acts[2])
-        L.append("  const double c2 = w * s2;")
-        L += [f"  {gp}h{i}_{j} += c2 * ({T}_W1T[j * {nin} + {i}] * {T}_W1T[j * {nin} + {j}]);" for i, j in d2]
-    L.append("}")
-    for (k, i, j), node in members.items():
-        names[node.uid] = f"{gp}v" if k == "v" else (f"{gp}g{i}" if k == "d" else f"{gp}h{i}_{j}")
-    return [indent + l for l in L]
-
-
-def _emit_rbf_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
-                      names: Dict[int, str], indent: str) -> List[str]:
-    """One loop over the training points of an RBF network with direct differences
-    ``z_i - T_ji`` (no cancellation on one lane), only the used entries."""
-    net = _NETWORKS[nid]
-    T = f"ANN{nid}"
-    nin, NT = net.n_in, net.NT
-    d1 = sorted(i for (k, i, _) in members if k == "d")
-    d2 = sorted((i, j) for (k, i, j) in members if k == "dd")
-    need_v = ("v", -1, -1) in members
-    L = [f"const double {gp}z{i} = ({x[i]}) * {_c_literal(net.s[i])} + {_c_literal(net.t[i])};" for i in range(nin)]
-    if need_v:
-        L.append(f"double {gp}v = 0.0;")
-    L += [f"double {gp}g{i} = 0.0;" for i in d1]
-    L += [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
-    L.append("#pragma unroll 4")
-    L.append(f"for (int j = 0; j < {NT}; ++j) {{")
-    L += [f"  const double d{i} = {gp}z{i} - {T}_T[j * {nin} + {i}];" for i in range(nin)]
-    L.append(f"  const double w = {T}_A[j] * exp(-0.5 * ({' + '.join(f'd{i} * d{i}' for i in range(nin))}));")
-    if need_v:
-        L.append(f"  {gp}v += w;")
-    L += [f"  {gp}g{i} += w * d{i};" for i in d1]
-    L += [f"  {gp}h{i}_{j} += w * (d{i} * d{j}{' - 1.0' if i == j else ''});" for i, j in d2]
-    L.append("}")
-    L += [f"{gp}g{i} *= {_c_literal(-net.s[i])};" for i in d1]
-    L += [f"{gp}h{i}_{j} *= {_c_literal(net.s[i] * net.s[j])};" for i, j in d2]
-    for (k, i, j), node in members.items():
-        names[node.uid] = f"{gp}v" if k == "v" else (f"{gp}g{i}" if k == "d" else f"{gp}h{i}_{j}")
-    return [indent + l for l in L]
-
-
-def _emit_deep_network(nid: int, x: List[str], members: Dict[tuple, Expr], gp: str,
-                       names: Dict[int, str], indent: str) -> List[str]:
-    """Loops over the units of the two hidden layers of a :class:`DeepNetwork` on one lane:
-    forward pass, ``u = W2 c1`` when a derivative is used, one Jacobian column ``J[:, i]`` per
-    input that occurs in a used pair; only the used entries."""
-    net = _NETWORKS[nid]
-    T = f"ANN{nid}"
-    nin, H1, H2 = net.n_in, net.H1, net.H2
-    d1 = sorted(i for (k, i, _) in members if k == "d")
-    d2 = sorted((i, j) for (k, i, j) in members if k == "dd")
-    need_v = ("v", -1, -1) in members
-    a1, a2 = _ACT_C[net.act1], _ACT_C[net.act2]
-    L = [f"double {gp}s0[{H1}];"]
-    if d1 or d2:
-        L.append(f"double {gp}s1[{H1}];")
-    if d2:
-        L.append(f"double {gp}s2[{H1}];")
-    L.append(f"for (int j = 0; j < {H1}; ++j) {{")
-    pre = " + ".join([f"{T}_B1[j]"] + [f"({x[i]}) * {T}_W1T[j * {nin} + {i}]" for i in range(nin)
-                                        if np.any(net.W1[i] != 0.0)])
-    L.append(f"  const double a = {pre};")
-    L.append("  " + a1[0])
-    L.append(f"  {gp}s0[j] = s0;")
-    if d1 or d2:
-        L += ["  " + a1[1], f"  {gp}s1[j] = s1;"]
-    if d2:
-        L += ["  " + a1[2], f"  {gp}s2[j] = s2;"]
-    L.append("}")
-    if need_v:
-        L.append(f"double {gp}v = {_c_literal(net.b3)};")
-    if d1 or d2:
-        L.append(f"double {gp}c1[{H2}];")
-    if d2:
-        L.append(f"double {gp}c2[{H2}];")
-    L.append(f"for (int k = 0; k < {H2}; ++k) {{")
-    L.append(f"  double a = {T}_B2[k];")
-    L.append(f"  for (int j = 0; j < {H1}; ++j) a += {gp}s0[j] * {T}_W2[j * {H2} + k];")
-    L.append(f"  const double w = {T}_W3[k];")
-    L.append("  " + a2[0])
-    if need_v:
-        L.append(f"  {gp}v += w * s0;")
-    if d1 or d2:
-        L += ["  " + a2[1], f"  {gp}c1[k] = w * s1;"]
-    if d2:
-        L += ["  " + a2[2], f"  {gp}c2[k] = w * s2;"]
-    L.append("}")
-    if d1 or d2:
-        L.append(f"double {gp}u[{H1}];")
-        L.append(f"for (int j = 0; j < {H1}; ++j) {{")
-        L.append("  double u = 0.0;")
-        L.append(f"  for (int k = 0; k < {H2}; ++k) u += {T}_W2[j * {H2} + k] * {gp}c1[k];")
-        L.append(f"  {gp}u[j] = u;")
-        L.append("}")
-    L += [f"double {gp}g{i} = 0.0;" for i in d1]
-    L += [f"double {gp}h{i}_{j} = 0.0;" for i, j in d2]
-    if d1 or d2:
-        L.append(f"for (int j = 0; j < {H1}; ++j) {{")
-        if d1:
-            L.append(f"  const double e1 = {gp}s1[j] * {gp}u[j];")
-            L += [f"  {gp}g{i} += e1 * {T}_W1T[j * {nin} + {i}];" for i in d1]
-        if d2:
-            L.append(f"  const double e2 = {gp}s2[j] * {gp}u[j];")
-            L += [f"  {gp}h{i}_{j} += e2 * ({T}_W1T[j * {nin} + {i}] * {T}_W1T[j * {nin} + {j}]);" for i, j in d2]
-        L.append("}")
-    if d2:
-        cols = sorted({i for p in d2 for i in p})
-        L.append(f"for (int k = 0; k < {H2}; ++k) {{")
-        L += [f"  double J{i} = 0.0;" for i in cols]
-        L.append(f"  for (int j = 0; j < {H1}; ++j) {{")
-        L.append(f"    const double w = {T}_W2[j * {H2} + k] * {gp}s1[j];")
-        L += [f"    J{i} += w * {T}_W1T[j * {nin} + {i}];" for i in cols]
-        L.append("  }")
-        L += [f"  {gp}h{i}_{j} += {gp}c2[k] * (J{i} * J{j});" for i, j in d2]
-        L.append("}")
+    L = _NETWORKS[nid].emit_lane(f"ANN{nid}", x, ("v", -1, -1) in members, d1, d2, gp)
     for (k, i, j), node in members.items():
         names[node.uid] = f"{gp}v" if k == "v" else (f"{gp}g{i}" if k == "d" else f"{gp}h{i}_{j}")
     return [indent + l for l in L]
 
 
 def network_tables(net_ids) -> List[str]:
-    """``__constant__`` weight tables of the networks (W1 transposed: [H][n_in]; a two-hidden-layer
-    network adds ``W2 [H1][H2]`` in that one orientation, ``B2`` and ``W3``; an RBF
-    network: the training points ``T [NT][n_in]``, the coefficients ``A [NT]``, and for the wave
-    pass ``TT [NT] = -1/2 |T_j|^2`` and the input map ``S``, ``SH`` [n_in])."""
-    out = []
-    for nid in sorted(net_ids):
-        net = _NETWORKS[nid]
-        if isinstance(net, RBFNetwork):
-            lit = lambda v: ", ".join(_c_literal(float(u)) for u in np.asarray(v).reshape(-1))
-            out += [f"__constant__ double ANN{nid}_T[{net.NT * net.n_in}] = {{{lit(net.T)}}};",
-                    f"__constant__ double ANN{nid}_A[{net.NT}] = {{{lit(net.a)}}};",
-                    f"__constant__ double ANN{nid}_TT[{net.NT}] = {{{lit(net.tt)}}};",
-                    f"__constant__ double ANN{nid}_S[{net.n_in}] = {{{lit(net.s)}}};",
-                    f"__constant__ double ANN{nid}_SH[{net.n_in}] = {{{lit(net.t)}}};"]
-            continue
-        if isinstance(net, DeepNetwork):
-            lit = lambda v: ", ".join(_c_literal(float(u)) for u in np.asarray(v).reshape(-1))
-            out += [f"__constant__ double ANN{nid}_W1T[{net.H1 * net.n_in}] = {{{lit(net.W1.T)}}};",
-                    f"__constant__ double ANN{nid}_B1[{net.H1}] = {{{lit(net.b1)}}};",
-                    f"__constant__ double ANN{nid}_W2[{net.H1 * net.H2}] = {{{lit(net.W2)}}};",
-                    f"__constant__ double ANN{nid}_B2[{net.H2}] = {{{lit(net.b2)}}};",
-                    f"__constant__ double ANN{nid}_W3[{net.H2}] = {{{lit(net.w3)}}};"]
-            continue
-        w1t = ", ".join(_c_literal(v) for v in net.W1.T.reshape(-1))
-        b1 = ", ".join(_c_literal(v) for v in net.b1)
-        w2 = ", ".join(_c_literal(v) for v in net.w2)
-        out += [f"__constant__ double ANN{nid}_W1T[{net.H * net.n_in}] = {{{w1t}}};",
-                f"__constant__ double ANN{nid}_B1[{net.H}] = {{{b1}}};",
-                f"__constant__ double ANN{nid}_W2[{net.H}] = {{{w2}}};"]
-    return out
+    """``__constant__`` weight tables of the networks, as each kind's ``tables()`` lists them (W1
+    transposed: [H][n_in]; a two-hidden-layer network adds ``W2 [H1][H2]`` in that one
+    orientation, ``B2`` and ``W3``; an RBF network: the training points ``T [NT][n_in]``, the
+    coefficients ``A [NT]``, and for the wave pass ``TT [NT] = -1/2 |T_j|^2`` and the input map
+    ``S``, ``SH`` [n_in])."""
+    return [_c_table(f"ANN{nid}_{suffix}", np.asarray(table, dtype=float))
+            for nid in sorted(net_ids) for suffix, table in _NETWORKS[nid].tables()]
 
 
 def _c_op(op: str, a: List[str]) -> str:

@@ -1,13 +1,9 @@
 """Unit harness for ``mpcx_net::eval2`` (csrc/mpcx_net_mfma.h, two hidden layers): the config
 table, the HIP source generated from it, its build, the seeded inputs and the high-precision
-reference.  Modelled on tests/net_eval_harness.py, whose build, mpmath helpers and error
-measure it shares.
+reference.
 
-One wavefront per workgroup evaluates one input set: it stages ``X[R][NIN]`` in LDS, fills the
-LDS output array ``V[R] | G[R][ND1] | Hd[R][ND2]`` with NaN, puts a sentinel into 8 guard
-doubles behind either array, calls ``eval2`` as the generated ``gen_net_<kind>`` functions do,
-and copies both arrays with their guards back to global memory.  Weights and tables stay in
-global memory (one set of tables per input set).
+The kernel wrapper, launcher and build are those of tests/eval_harness_core.py (one set of
+tables per input set).
 
 The reference evaluates the defining formulas in mpmath at 60 digits,
 
@@ -22,17 +18,16 @@ absolute value (a cancellation-free bound for act'').
 
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 import functools
-import hashlib
 from typing import List, Optional, Tuple
 
 import mpmath as mp
 import numpy as np
 
-from tests.net_eval_harness import (ACTS, DPS, EPS, GUARD, NB, SENTINEL, _act_terms, _m, build_source,  # noqa: F401
-                                    scaled_error)
+from tests import eval_harness_core as core
+from tests.eval_harness_core import ACTS, DPS, EPS, GUARD, SENTINEL, _m, scaled_error  # noqa: F401
+from tests.net_eval_harness import NB, _act_terms
 
 #: largest |pre-activation| of either layer per input set (moderate, saturated, zero inputs): the
 #: first layer's by scaling the inputs and its bias, the second layer's by scaling W2 and b2 of
@@ -41,7 +36,7 @@ TARGETS = ((3.0, 3.0), (20.0, 20.0), (None, 3.0))
 
 
 @dataclasses.dataclass(frozen=True)
-class Config:
+class Config(core.ConfigBase):
     R: int
     NIN: int
     H1: int
@@ -61,44 +56,11 @@ class Config:
         return (f"r{self.R}_i{self.NIN}_h{self.H1}_{self.H2}_{self.act1}_{self.act2}_"
                 f"{'v' if self.WV else 'nov'}_g{self.ND1}_p{self.ND2}")
 
-    @property
-    def seed(self) -> int:
-        return int(hashlib.sha1(self.name.encode()).hexdigest()[:8], 16)
-
-    @property
-    def nx(self) -> int:
-        return self.R * self.NIN
-
-    @property
-    def nout(self) -> int:
-        return self.R * (1 + self.ND1 + self.ND2)
-
     def d1(self) -> List[int]:
-        """Sorted distinct input indices; a strict subset skips input 0 and keeps the last."""
-        if self.d1_fixed is not None:
-            return list(self.d1_fixed)
-        if self.ND1 == self.NIN:
-            return list(range(self.NIN))
-        if self.ND1 == 0:
-            return []
-        rng = np.random.default_rng(self.seed + 1)
-        rest = rng.choice(np.arange(1, self.NIN - 1), self.ND1 - 1, replace=False)
-        return sorted([int(i) for i in rest] + [self.NIN - 1])
+        return list(self.d1_fixed) if self.d1_fixed is not None else super().d1()
 
     def pairs(self) -> List[Tuple[int, int]]:
-        """Sorted pairs (a >= b) with (NIN-1, NIN-1), an off-diagonal and another diagonal one."""
-        if self.pairs_fixed is not None:
-            return [tuple(p) for p in self.pairs_fixed]
-        every = [(a, b) for a in range(self.NIN) for b in range(a + 1)]
-        if self.ND2 >= len(every):
-            assert self.ND2 == len(every)
-            return every
-        must = [(self.NIN - 1, self.NIN - 1), (self.NIN - 1, 0), (0, 0)]
-        must = list(dict.fromkeys(p for p in must if p in every))[:self.ND2]
-        rest = [p for p in every if p not in must]
-        rng = np.random.default_rng(self.seed + 2)
-        pick = rng.choice(len(rest), self.ND2 - len(must), replace=False)
-        return sorted(must + [rest[int(i)] for i in pick])
+        return [tuple(p) for p in self.pairs_fixed] if self.pairs_fixed is not None else super().pairs()
 
 
 #: the instantiations, each chosen for the edge named (the single source of the generated
@@ -125,73 +87,27 @@ assert len(BY_NAME) == len(CONFIGS) <= 16
 # the HIP source and its build
 # ---------------------------------------------------------------------------
 
-_PRELUDE = f"""// generated by tests/deep_eval_harness.py: one kernel and launcher per config
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include "mpcx_net_mfma.h"
-
-#define HARNESS_GUARD {GUARD}
-#define HARNESS_SENTINEL ({SENTINEL!r})
-
-template <int R, int NIN, int H1, int H2, int ACT1, int ACT2, bool WV, int ND1, int ND2>
-__global__ void __launch_bounds__(64) deep_eval_kernel(
-    const double* __restrict__ X, const double* __restrict__ W1T, const double* __restrict__ B1,
-    const double* __restrict__ W2, const double* __restrict__ B2, const double* __restrict__ W3,
-    const double* __restrict__ b3, const int* __restrict__ D1, const double* __restrict__ PW,
-    const int* __restrict__ P2, double* __restrict__ Xback, double* __restrict__ Oback) {{
-  constexpr int NX = R * NIN, NO = R * (1 + ND1 + ND2), G = HARNESS_GUARD;
-  __shared__ double sx[NX + G];
-  __shared__ double so[NO + G];
-  const int lane = threadIdx.x, set = blockIdx.x;
-  for (int i = lane; i < NX; i += 64) sx[i] = X[set * NX + i];
-  for (int i = lane; i < NO; i += 64) so[i] = __builtin_nan("");
-  if (lane < G) {{ sx[NX + lane] = HARNESS_SENTINEL; so[NO + lane] = HARNESS_SENTINEL; }}
-  __syncthreads();
-  mpcx_net::eval2<R, NIN, H1, H2, ACT1, ACT2, WV, ND1, ND2>(
-      (const mpcx_net::ldsd*)sx, (mpcx_net::ldsd*)so, (mpcx_net::ldsd*)(so + R),
-      (mpcx_net::ldsd*)(so + R + R * ND1), W1T + set * (H1 * NIN), B1 + set * H1, W2 + set * (H1 * H2),
-      B2 + set * H2, W3 + set * H2, b3[set], D1, ND2 > 0 ? PW + set * (ND2 * H1) : nullptr, P2, lane);
-  __syncthreads();
-  for (int i = lane; i < NX + G; i += 64) Xback[set * (NX + G) + i] = sx[i];
-  for (int i = lane; i < NO + G; i += 64) Oback[set * (NO + G) + i] = so[i];
-}}
-"""
-
-_LAUNCHER = """
-extern "C" int launch_{name}(const double* X, const double* W1T, const double* B1, const double* W2,
-                             const double* B2, const double* W3, const double* b3, const int* D1,
-                             const double* PW, const int* P2, double* Xback, double* Oback, int nb) {{
-  hipLaunchKernelGGL((deep_eval_kernel<{R}, {NIN}, {H1}, {H2}, {ACT1}, {ACT2}, {WV}, {ND1}, {ND2}>), dim3(nb),
-                     dim3(64), 0, 0, X, W1T, B1, W2, B2, W3, b3, D1, PW, P2, Xback, Oback);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
-}}
-"""
-
-NARGS = 12   # pointer arguments of a launcher
+KERNEL = core.Kernel(
+    "deep_eval", "eval2",
+    (("int", "R"), ("int", "NIN"), ("int", "H1"), ("int", "H2"), ("int", "ACT1"), ("int", "ACT2"), ("bool", "WV"),
+     ("int", "ND1"), ("int", "ND2")),
+    (("double", "W1T"), ("double", "B1"), ("double", "W2"), ("double", "B2"), ("double", "W3"), ("double", "b3"),
+     ("int", "D1"), ("double", "PW"), ("int", "P2")),
+    "W1T + set * (H1 * NIN), B1 + set * H1, W2 + set * (H1 * H2), B2 + set * H2, W3 + set * H2, b3[set], D1, "
+    "ND2 > 0 ? PW + set * (ND2 * H1) : nullptr, P2")
 
 
 def generate_source(configs=CONFIGS) -> str:
-    parts = [_PRELUDE]
-    for c in configs:
-        parts.append(_LAUNCHER.format(name=c.name, R=c.R, NIN=c.NIN, H1=c.H1, H2=c.H2, ACT1=ACTS.index(c.act1),
-                                      ACT2=ACTS.index(c.act2), WV="true" if c.WV else "false", ND1=c.ND1,
-                                      ND2=c.ND2))
-    return "".join(parts)
+    return KERNEL.source(configs)
 
 
 def build(include_dir=None, configs=CONFIGS):
-    """Compile the harness (``net_eval_harness.build_source``)."""
-    return build_source(generate_source(configs), "deep_eval", include_dir)
+    """Compile the harness (``eval_harness_core.build_source``)."""
+    return KERNEL.build(configs, include_dir)
 
 
-def load(lib_path) -> ctypes.CDLL:
-    lib = ctypes.CDLL(str(lib_path))
-    for c in CONFIGS:
-        fn = getattr(lib, f"launch_{c.name}", None)
-        if fn is not None:
-            fn.argtypes = [ctypes.c_void_p] * NARGS + [ctypes.c_int]
-            fn.restype = ctypes.c_int
-    return lib
+def load(lib_path):
+    return core.load(lib_path, CONFIGS, KERNEL.nargs)
 
 
 # ---------------------------------------------------------------------------
@@ -324,21 +240,10 @@ def numpy_outputs(name: str, s: int):
 
 def errors_of(name: str, outputs) -> dict:
     """{"V" | "G" | "H": scaled error, max over the input sets}; ``outputs(s) -> (V, G, H)``."""
-    ref = reference(name)
-    err = {}
-    for s in range(NB):
-        for kind, got, rs in zip("VGH", outputs(s), (ref.V[s], ref.G[s], ref.H[s])):
-            if rs is not None and got is not None:
-                err[kind] = max(err.get(kind, 0.0), scaled_error(got, rs))
-    return err
-
-
-def fp64_errors() -> dict:
-    """The unit of the tolerance: scaled error of the plain fp64 evaluation, per config and kind."""
-    return {c.name: errors_of(c.name, functools.partial(numpy_outputs, c.name)) for c in CONFIGS}
+    return core.errors_of(reference(name), outputs, range(NB))
 
 
 if __name__ == "__main__":   # prints the content of tests/golden/deep_eval_fp64_error.json
-    import json
+    import sys
 
-    print(json.dumps(fp64_errors(), indent=1))
+    core.print_fp64_errors(sys.modules[__name__])

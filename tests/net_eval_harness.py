@@ -1,11 +1,7 @@
 """Unit harness for ``mpcx_net::eval`` (csrc/mpcx_net_mfma.h): the config table, the HIP
 source generated from it, its build, the seeded inputs and the high-precision reference.
 
-One wavefront per workgroup evaluates one input set: it stages ``X[R][NIN]`` in LDS, fills the
-LDS output array ``V[R] | G[R][ND1] | Hd[R][ND2]`` with NaN, puts a sentinel into 8 guard
-doubles behind either array, calls ``eval`` with the LDS pointers cast to ``mpcx_net::ldsd*``
-as the generated ``gen_net_<kind>`` functions do, and copies both arrays with their guards
-back to global memory.  Weights and tables stay in global memory.
+The kernel wrapper, launcher and build are those of tests/eval_harness_core.py.
 
 The reference evaluates the defining formulas
 ``v = b2 + sum_j w2_j act(a_j)``, ``g_i = sum_j w2_j act'(a_j) W1_ij``,
@@ -16,31 +12,21 @@ with every factor replaced by its absolute value (a cancellation-free bound for 
 
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 import functools
-import hashlib
-import os
-import pathlib
-import subprocess
-import tempfile
-from typing import List, Optional, Tuple
+from typing import List, Tuple
 
 import mpmath as mp
 import numpy as np
 
-from agentlib_mpc_amd.runtime import native
+from tests import eval_harness_core as core
+from tests.eval_harness_core import ACTS, DPS, EPS, GUARD, SENTINEL, _m, build_source, scaled_error  # noqa: F401
 
-ACTS = ("sigmoid", "tanh", "linear", "softplus", "exponential", "gaussian")  # codes 0..5
 NB = 3           # input sets per config: moderate, saturated, zero
-GUARD = 8        # guard doubles behind either LDS array
-SENTINEL = -7.25e77
-EPS = float(np.finfo(np.float64).eps)
-DPS = 60
 
 
 @dataclasses.dataclass(frozen=True)
-class Config:
+class Config(core.ConfigBase):
     R: int
     NIN: int
     H: int
@@ -55,41 +41,6 @@ class Config:
     def name(self) -> str:
         return (f"r{self.R}_i{self.NIN}_h{self.H}_{self.act}_{'v' if self.WV else 'nov'}"
                 f"_g{self.ND1}_p{self.ND2}")
-
-    @property
-    def seed(self) -> int:
-        return int(hashlib.sha1(self.name.encode()).hexdigest()[:8], 16)
-
-    @property
-    def nx(self) -> int:
-        return self.R * self.NIN
-
-    @property
-    def nout(self) -> int:
-        return self.R * (1 + self.ND1 + self.ND2)
-
-    def d1(self) -> List[int]:
-        """Sorted distinct input indices; a strict subset skips input 0 and keeps the last."""
-        if self.ND1 == self.NIN:
-            return list(range(self.NIN))
-        if self.ND1 == 0:
-            return []
-        rng = np.random.default_rng(self.seed + 1)
-        rest = rng.choice(np.arange(1, self.NIN - 1), self.ND1 - 1, replace=False)
-        return sorted([int(i) for i in rest] + [self.NIN - 1])
-
-    def pairs(self) -> List[Tuple[int, int]]:
-        """Sorted pairs (a >= b) with (NIN-1, NIN-1), an off-diagonal and another diagonal one."""
-        every = [(a, b) for a in range(self.NIN) for b in range(a + 1)]
-        if self.ND2 >= len(every):
-            assert self.ND2 == len(every)
-            return every
-        must = [(self.NIN - 1, self.NIN - 1), (self.NIN - 1, 0), (0, 0)]
-        must = list(dict.fromkeys(p for p in must if p in every))[:self.ND2]
-        rest = [p for p in every if p not in must]
-        rng = np.random.default_rng(self.seed + 2)
-        pick = rng.choice(len(rest), self.ND2 - len(must), replace=False)
-        return sorted(must + [rest[int(i)] for i in pick])
 
 
 #: the instantiations, each chosen for the edge named (the single source of the generated
@@ -114,107 +65,24 @@ assert len(BY_NAME) == len(CONFIGS) <= 16
 # the HIP source and its build
 # ---------------------------------------------------------------------------
 
-_PRELUDE = f"""// generated by tests/net_eval_harness.py: one kernel and launcher per config
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include "mpcx_net_mfma.h"
-
-#define HARNESS_GUARD {GUARD}
-#define HARNESS_SENTINEL ({SENTINEL!r})
-
-template <int R, int NIN, int H, int ACT, bool WV, int ND1, int ND2>
-__global__ void __launch_bounds__(64) net_eval_kernel(
-    const double* __restrict__ X, const double* __restrict__ W1T, const double* __restrict__ B1,
-    const double* __restrict__ W2, const double* __restrict__ b2, const int* __restrict__ D1,
-    const double* __restrict__ PW, double* __restrict__ Xback, double* __restrict__ Oback) {{
-  constexpr int NX = R * NIN, NO = R * (1 + ND1 + ND2), G = HARNESS_GUARD;
-  __shared__ double sx[NX + G];
-  __shared__ double so[NO + G];
-  const int lane = threadIdx.x, set = blockIdx.x;
-  for (int i = lane; i < NX; i += 64) sx[i] = X[set * NX + i];
-  for (int i = lane; i < NO; i += 64) so[i] = __builtin_nan("");
-  if (lane < G) {{ sx[NX + lane] = HARNESS_SENTINEL; so[NO + lane] = HARNESS_SENTINEL; }}
-  __syncthreads();
-  mpcx_net::eval<R, NIN, H, ACT, WV, ND1, ND2>(
-      (const mpcx_net::ldsd*)sx, (mpcx_net::ldsd*)so, (mpcx_net::ldsd*)(so + R),
-      (mpcx_net::ldsd*)(so + R + R * ND1), W1T + set * (H * NIN), B1 + set * H, W2 + set * H, b2[set], D1,
-      ND2 > 0 ? PW + set * (ND2 * H) : nullptr, lane);
-  __syncthreads();
-  for (int i = lane; i < NX + G; i += 64) Xback[set * (NX + G) + i] = sx[i];
-  for (int i = lane; i < NO + G; i += 64) Oback[set * (NO + G) + i] = so[i];
-}}
-"""
-
-_LAUNCHER = """
-extern "C" int launch_{name}(const double* X, const double* W1T, const double* B1, const double* W2,
-                             const double* b2, const int* D1, const double* PW, double* Xback,
-                             double* Oback, int nb) {{
-  hipLaunchKernelGGL((net_eval_kernel<{R}, {NIN}, {H}, {ACT}, {WV}, {ND1}, {ND2}>), dim3(nb), dim3(64), 0, 0,
-                     X, W1T, B1, W2, b2, D1, PW, Xback, Oback);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
-}}
-"""
+KERNEL = core.Kernel(
+    "net_eval", "eval",
+    (("int", "R"), ("int", "NIN"), ("int", "H"), ("int", "ACT"), ("bool", "WV"), ("int", "ND1"), ("int", "ND2")),
+    (("double", "W1T"), ("double", "B1"), ("double", "W2"), ("double", "b2"), ("int", "D1"), ("double", "PW")),
+    "W1T + set * (H * NIN), B1 + set * H, W2 + set * H, b2[set], D1, ND2 > 0 ? PW + set * (ND2 * H) : nullptr")
 
 
 def generate_source(configs=CONFIGS) -> str:
-    parts = [_PRELUDE]
-    for c in configs:
-        parts.append(_LAUNCHER.format(name=c.name, R=c.R, NIN=c.NIN, H=c.H, ACT=ACTS.index(c.act),
-                                      WV="true" if c.WV else "false", ND1=c.ND1, ND2=c.ND2))
-    return "".join(parts)
+    return KERNEL.source(configs)
 
 
-def _cache_dir() -> pathlib.Path:
-    for d in (native.BUILD_DIR / "net_eval_harness",
-              pathlib.Path(tempfile.gettempdir()) / f"mpcx_net_eval_harness_{os.getuid()}"):
-        try:
-            d.mkdir(parents=True, exist_ok=True)
-            if os.access(d, os.W_OK):
-                return d
-        except OSError:
-            continue
-    raise RuntimeError("no writable directory for the harness build")
+def build(include_dir=None, configs=CONFIGS):
+    """Compile the harness (``eval_harness_core.build_source``)."""
+    return KERNEL.build(configs, include_dir)
 
 
-def build_source(source: str, stem: str, include_dir: Optional[os.PathLike] = None) -> pathlib.Path:
-    """Compile a harness source with the flags of ``native.build_library`` (cached by the hash of
-    the source, the header and the command) into ``<stem>_<hash>.so``.  ``include_dir``: where
-    mpcx_net_mfma.h is taken from."""
-    csrc = pathlib.Path(include_dir) if include_dir is not None else native.CSRC
-    flags = ["-shared", "-fPIC", f"--offload-arch={native.OFFLOAD_ARCH}", "-O3", "-std=c++17",
-             f"-I{native.INCLUDE}", f"-I{csrc}"]
-    key = hashlib.sha1()
-    for part in (source.encode(), (csrc / "mpcx_net_mfma.h").read_bytes(), " ".join(flags).encode()):
-        key.update(part)
-    d = _cache_dir()
-    name = f"{stem}_{key.hexdigest()[:12]}"
-    lib = d / f"{name}.so"
-    if lib.exists():
-        return lib
-    src = d / f"{name}.hip"
-    src.write_text(source)
-    tmp = d / f"{name}.{os.getpid()}.so.tmp"
-    res = subprocess.run([native._hipcc(), *flags, str(src), "-o", str(tmp)], capture_output=True, text=True)
-    if res.returncode != 0:
-        tmp.unlink(missing_ok=True)
-        raise RuntimeError(f"building the {stem.replace('_', ' ')} harness failed:\n{res.stderr[-4000:]}")
-    os.replace(tmp, lib)
-    return lib
-
-
-def build(include_dir: Optional[os.PathLike] = None, configs=CONFIGS) -> pathlib.Path:
-    """Compile the harness (:func:`build_source`)."""
-    return build_source(generate_source(configs), "net_eval", include_dir)
-
-
-def load(lib_path) -> ctypes.CDLL:
-    lib = ctypes.CDLL(str(lib_path))
-    for c in CONFIGS:
-        fn = getattr(lib, f"launch_{c.name}", None)
-        if fn is not None:
-            fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int]
-            fn.restype = ctypes.c_int
-    return lib
+def load(lib_path):
+    return core.load(lib_path, CONFIGS, KERNEL.nargs)
 
 
 # ---------------------------------------------------------------------------
@@ -269,11 +137,6 @@ def inputs(name: str) -> Inputs:
 # ---------------------------------------------------------------------------
 # the reference (mpmath)
 # ---------------------------------------------------------------------------
-
-def _m(x) -> np.ndarray:
-    """fp64 array -> object array of mpf (exact)."""
-    return np.frompyfunc(lambda v: mp.mpf(float(v)), 1, 1)(np.asarray(x, dtype=float))
-
 
 def _act_terms(act: str, a):
     """act(a), act'(a), act''(a) and a cancellation-free bound of |act''(a)|, from the
@@ -333,24 +196,6 @@ def reference(name: str) -> Reference:
     return out
 
 
-def scaled_error(got: np.ndarray, ref_scale) -> float:
-    """max over elements of |got - ref| / S; where S is 0 the value must be exactly 0."""
-    ref, S = ref_scale
-    got = np.asarray(got, dtype=float)
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    worst = 0.0
-    with mp.workdps(DPS):
-        for g, r, s in zip(got.ravel(), ref.ravel(), S.ravel()):
-            if not np.isfinite(g):
-                return float("inf")
-            if s == 0:
-                if g != 0.0:
-                    return float("inf")
-                continue
-            worst = max(worst, float(abs(mp.mpf(float(g)) - r) / s))
-    return worst
-
-
 def numpy_outputs(name: str, s: int):
     """(V, G[:, d1], H[:, pairs]) of ``symbolic.Network.evaluate`` (plain fp64) on input set s."""
     from agentlib_mpc_amd import symbolic as sx
@@ -364,21 +209,10 @@ def numpy_outputs(name: str, s: int):
 
 def errors_of(name: str, outputs) -> dict:
     """{"V" | "G" | "H": scaled error, max over the input sets}; ``outputs(s) -> (V, G, H)``."""
-    ref = reference(name)
-    err = {}
-    for s in range(NB):
-        for kind, got, rs in zip("VGH", outputs(s), (ref.V[s], ref.G[s], ref.H[s])):
-            if rs is not None and got is not None:
-                err[kind] = max(err.get(kind, 0.0), scaled_error(got, rs))
-    return err
-
-
-def fp64_errors() -> dict:
-    """The unit of the tolerance: scaled error of the plain fp64 evaluation, per config and kind."""
-    return {c.name: errors_of(c.name, functools.partial(numpy_outputs, c.name)) for c in CONFIGS}
+    return core.errors_of(reference(name), outputs, range(NB))
 
 
 if __name__ == "__main__":   # prints the content of tests/golden/net_eval_fp64_error.json
-    import json
+    import sys
 
-    print(json.dumps(fp64_errors(), indent=1))
+    core.print_fp64_errors(sys.modules[__name__])

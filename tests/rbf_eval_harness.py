@@ -1,13 +1,8 @@
 """Unit harness for ``mpcx_net::eval_rbf`` (csrc/mpcx_net_mfma.h): the config table, the HIP
 source generated from it, its build, the seeded inputs and the high-precision reference.
-Modelled on tests/net_eval_harness.py, which supplies what can be shared.
 
-One wavefront per workgroup evaluates one input set: it stages ``X[R][NIN]`` in LDS, fills the
-LDS output array ``V[R] | G[R][ND1] | Hd[R][ND2]`` with NaN, puts a sentinel into 8 guard
-doubles behind either array, calls ``eval_rbf`` with the LDS pointers cast to
-``mpcx_net::ldsd*`` as the generated ``gen_net_<kind>`` functions do, and copies both arrays
-with their guards back to global memory.  The tables (``T``, ``TT``, ``A``, ``S``, ``SH``,
-one of each per input set) stay in global memory.
+The kernel wrapper, launcher and build are those of tests/eval_harness_core.py; the tables
+(``T``, ``TT``, ``A``, ``S``, ``SH``, one of each per input set) stay in global memory.
 
 The reference evaluates the direct-difference formulas, ``z = s o x + t``, ``d_j = z - T_j``,
 
@@ -29,19 +24,15 @@ noise: the fp64 unit of set 1 is therefore far above eps where the other weights
 
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 import functools
-import hashlib
-import os
-import pathlib
-from typing import List, Optional, Tuple
+from typing import List, Tuple
 
 import mpmath as mp
 import numpy as np
 
-from tests import net_eval_harness as nh
-from tests.net_eval_harness import DPS, EPS, GUARD, SENTINEL, _m, scaled_error  # noqa: F401
+from tests import eval_harness_core as core
+from tests.eval_harness_core import DPS, EPS, GUARD, SENTINEL, _m, scaled_error  # noqa: F401
 
 NB = 4                 # input sets per config: inside, on a training point, far, underflow
 CHECKED = (0, 1, 2)    # the sets compared with the reference (3: finite and below 1e-290)
@@ -50,7 +41,7 @@ UNDERFLOW_BOUND = 1e-290
 
 
 @dataclasses.dataclass(frozen=True)
-class Config:
+class Config(core.ConfigBase):
     R: int
     NIN: int
     NT: int
@@ -66,27 +57,10 @@ class Config:
                 f"{'_onehot' if self.onehot else ''}")
 
     @property
-    def seed(self) -> int:
-        return int(hashlib.sha1(self.name.encode()).hexdigest()[:8], 16)
-
-    @property
-    def nx(self) -> int:
-        return self.R * self.NIN
-
-    @property
-    def nout(self) -> int:
-        return self.R * (1 + self.ND1 + self.ND2)
-
-    def _twin(self) -> nh.Config:
-        return nh.Config(self.R, self.NIN, self.NT, "linear", self.WV, self.ND1, self.ND2, self.edge)
-
-    def d1(self) -> List[int]:
-        """Sorted distinct input indices; a strict subset skips input 0 and keeps the last."""
-        return self._twin().d1()
-
-    def pairs(self) -> List[Tuple[int, int]]:
-        """Sorted pairs (a >= b) with (NIN-1, NIN-1), an off-diagonal and another diagonal one."""
-        return self._twin().pairs()
+    def subset_seed(self) -> int:
+        # d1() and pairs() were drawn under the name of the one-layer config of the same shape
+        return core.name_seed(f"r{self.R}_i{self.NIN}_h{self.NT}_linear_{'v' if self.WV else 'nov'}"
+                              f"_g{self.ND1}_p{self.ND2}")
 
 
 #: the instantiations, each chosen for the edge named (the single source of the generated
@@ -109,70 +83,25 @@ assert len(BY_NAME) == len(CONFIGS)
 # the HIP source and its build
 # ---------------------------------------------------------------------------
 
-_PRELUDE = f"""// generated by tests/rbf_eval_harness.py: one kernel and launcher per config
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include "mpcx_net_mfma.h"
-
-#define HARNESS_GUARD {GUARD}
-#define HARNESS_SENTINEL ({SENTINEL!r})
-
-template <int R, int NIN, int NT, bool WV, int ND1, int ND2>
-__global__ void __launch_bounds__(64) rbf_eval_kernel(
-    const double* __restrict__ X, const double* __restrict__ T, const double* __restrict__ TT,
-    const double* __restrict__ A, const double* __restrict__ S, const double* __restrict__ SH,
-    const int* __restrict__ D1, const int* __restrict__ P2, double* __restrict__ Xback,
-    double* __restrict__ Oback) {{
-  constexpr int NX = R * NIN, NO = R * (1 + ND1 + ND2), G = HARNESS_GUARD;
-  __shared__ double sx[NX + G];
-  __shared__ double so[NO + G];
-  const int lane = threadIdx.x, set = blockIdx.x;
-  for (int i = lane; i < NX; i += 64) sx[i] = X[set * NX + i];
-  for (int i = lane; i < NO; i += 64) so[i] = __builtin_nan("");
-  if (lane < G) {{ sx[NX + lane] = HARNESS_SENTINEL; so[NO + lane] = HARNESS_SENTINEL; }}
-  __syncthreads();
-  mpcx_net::eval_rbf<R, NIN, NT, WV, ND1, ND2>(
-      (const mpcx_net::ldsd*)sx, (mpcx_net::ldsd*)so, (mpcx_net::ldsd*)(so + R),
-      (mpcx_net::ldsd*)(so + R + R * ND1), T + set * (NT * NIN), TT + set * NT, A + set * NT,
-      S + set * NIN, SH + set * NIN, D1, P2, lane);
-  __syncthreads();
-  for (int i = lane; i < NX + G; i += 64) Xback[set * (NX + G) + i] = sx[i];
-  for (int i = lane; i < NO + G; i += 64) Oback[set * (NO + G) + i] = so[i];
-}}
-"""
-
-_LAUNCHER = """
-extern "C" int launch_{name}(const double* X, const double* T, const double* TT, const double* A,
-                             const double* S, const double* SH, const int* D1, const int* P2,
-                             double* Xback, double* Oback, int nb) {{
-  hipLaunchKernelGGL((rbf_eval_kernel<{R}, {NIN}, {NT}, {WV}, {ND1}, {ND2}>), dim3(nb), dim3(64), 0, 0,
-                     X, T, TT, A, S, SH, D1, P2, Xback, Oback);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
-}}
-"""
+KERNEL = core.Kernel(
+    "rbf_eval", "eval_rbf",
+    (("int", "R"), ("int", "NIN"), ("int", "NT"), ("bool", "WV"), ("int", "ND1"), ("int", "ND2")),
+    (("double", "T"), ("double", "TT"), ("double", "A"), ("double", "S"), ("double", "SH"), ("int", "D1"),
+     ("int", "P2")),
+    "T + set * (NT * NIN), TT + set * NT, A + set * NT, S + set * NIN, SH + set * NIN, D1, P2")
 
 
 def generate_source(configs=CONFIGS) -> str:
-    parts = [_PRELUDE]
-    for c in configs:
-        parts.append(_LAUNCHER.format(name=c.name, R=c.R, NIN=c.NIN, NT=c.NT,
-                                      WV="true" if c.WV else "false", ND1=c.ND1, ND2=c.ND2))
-    return "".join(parts)
+    return KERNEL.source(configs)
 
 
-def build(include_dir: Optional[os.PathLike] = None, configs=CONFIGS) -> pathlib.Path:
-    """Compile the harness (``net_eval_harness.build_source``: same flags, cache and key)."""
-    return nh.build_source(generate_source(configs), "rbf_eval", include_dir)
+def build(include_dir=None, configs=CONFIGS):
+    """Compile the harness (``eval_harness_core.build_source``)."""
+    return KERNEL.build(configs, include_dir)
 
 
-def load(lib_path) -> ctypes.CDLL:
-    lib = ctypes.CDLL(str(lib_path))
-    for c in CONFIGS:
-        fn = getattr(lib, f"launch_{c.name}", None)
-        if fn is not None:
-            fn.argtypes = [ctypes.c_void_p] * 10 + [ctypes.c_int]
-            fn.restype = ctypes.c_int
-    return lib
+def load(lib_path):
+    return core.load(lib_path, CONFIGS, KERNEL.nargs)
 
 
 # ---------------------------------------------------------------------------
@@ -298,21 +227,10 @@ def numpy_outputs(name: str, s: int):
 
 def errors_of(name: str, outputs) -> dict:
     """{"V" | "G" | "H": scaled error, max over the checked input sets}; ``outputs(s) -> (V, G, H)``."""
-    ref = reference(name)
-    err = {}
-    for q, s in enumerate(CHECKED):
-        for kind, got, rs in zip("VGH", outputs(s), (ref.V[q], ref.G[q], ref.H[q])):
-            if rs is not None and got is not None:
-                err[kind] = max(err.get(kind, 0.0), scaled_error(got, rs))
-    return err
-
-
-def fp64_errors() -> dict:
-    """The unit of the tolerance: scaled error of the plain fp64 evaluation, per config and kind."""
-    return {c.name: errors_of(c.name, functools.partial(numpy_outputs, c.name)) for c in CONFIGS}
+    return core.errors_of(reference(name), outputs, CHECKED)
 
 
 if __name__ == "__main__":   # prints the content of tests/golden/rbf_eval_fp64_error.json
-    import json
+    import sys
 
-    print(json.dumps(fp64_errors(), indent=1))
+    core.print_fp64_errors(sys.modules[__name__])

@@ -12,26 +12,17 @@ regenerate with ``python -m tests.deep_eval_harness``), and never below a floor 
 bound of tests/test_net_eval.py.
 """
 
-import json
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+from tests import eval_harness_core as core
 from tests import deep_eval_harness as dh
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in dh.CONFIGS]
-FACTOR = 8.0
-FLOOR = 4.0 * dh.EPS
-
-with open(os.path.join(ROOT, "tests", "golden", "deep_eval_fp64_error.json")) as _f:
-    FP64_ERROR = json.load(_f)
-
-
-def _bound(name, kind):
-    return max(FACTOR * FP64_ERROR[name][kind], FLOOR)
+FP64_ERROR, _bound = core.golden("deep_eval")
 
 
 def test_config_tables_hit_the_edges():
@@ -98,46 +89,19 @@ def test_harness_source_compiles_for_gfx950():
 # GPU
 # ---------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def harness():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return dh.load(dh.build())
+harness = core.harness_fixture(dh)
 
 
 def run_config(lib, name):
     """Launch one config on its three input sets -> (Xback [NB, NX + GUARD], Oback [NB, NO + GUARD])."""
-    import torch
-
     c, inp = dh.BY_NAME[name], dh.inputs(name)
-    dev = torch.device("cuda:0")
-    up = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
-    X, W1T, B1, W2, B2, W3, b3 = up(inp.X), up(inp.W1T), up(inp.b1), up(inp.W2), up(inp.b2), up(inp.w3), up(inp.b3)
-    assert X.numel() == dh.NB * c.nx and W1T.numel() == dh.NB * c.H1 * c.NIN
-    assert W2.numel() == dh.NB * c.H1 * c.H2 and B1.numel() == dh.NB * c.H1
-    assert B2.numel() == W3.numel() == dh.NB * c.H2 and b3.numel() == dh.NB
-    D1 = up(inp.d1, torch.int32) if c.ND1 else None
-    PW = up(inp.PW) if c.ND2 else None
-    P2 = up(inp.P2, torch.int32) if c.ND2 else None
-    assert PW is None or (PW.numel() == dh.NB * c.ND2 * c.H1 and P2.numel() == 2 * c.ND2)
-    Xb = torch.zeros(dh.NB, c.nx + dh.GUARD, dtype=torch.float64, device=dev)
-    Ob = torch.zeros(dh.NB, c.nout + dh.GUARD, dtype=torch.float64, device=dev)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    torch.cuda.synchronize()
-    rc = getattr(lib, f"launch_{name}")(ptr(X), ptr(W1T), ptr(B1), ptr(W2), ptr(B2), ptr(W3), ptr(b3), ptr(D1),
-                                        ptr(PW), ptr(P2), ptr(Xb), ptr(Ob), dh.NB)
-    torch.cuda.synchronize()
-    assert rc == 0
-    return Xb.cpu().numpy(), Ob.cpu().numpy()
-
-
-def split_outputs(c, ob):
-    """One set's LDS output array -> V [R], G [R, ND1], Hd [R, ND2], guard."""
-    R = c.R
-    v, g, h = ob[:R], ob[R:R + R * c.ND1], ob[R + R * c.ND1:c.nout]
-    return v, g.reshape(R, c.ND1), h.reshape(R, c.ND2), ob[c.nout:]
+    assert inp.W1T.size == dh.NB * c.H1 * c.NIN
+    assert inp.W2.size == dh.NB * c.H1 * c.H2 and inp.b1.size == dh.NB * c.H1
+    assert inp.b2.size == inp.w3.size == dh.NB * c.H2 and inp.b3.size == dh.NB
+    assert inp.PW.size == dh.NB * c.ND2 * c.H1 and inp.P2.size == 2 * c.ND2
+    return core.launch(lib, c, dh.NB, inp.X, [inp.W1T, inp.b1, inp.W2, inp.b2, inp.w3, inp.b3,
+                                              inp.d1 if c.ND1 else None, inp.PW if c.ND2 else None,
+                                              inp.P2 if c.ND2 else None])
 
 
 @pytest.mark.gpu
@@ -145,18 +109,8 @@ def split_outputs(c, ob):
 def test_eval2_matches_reference(name, harness):
     c, inp = dh.BY_NAME[name], dh.inputs(name)
     xb, ob = run_config(harness, name)
-    outs = [split_outputs(c, ob[s]) for s in range(dh.NB)]
-    for s in range(dh.NB):
-        v, g, h, guard = outs[s]
-        # the guards of both LDS arrays and the LDS input are untouched
-        assert np.array_equal(guard, np.full(dh.GUARD, dh.SENTINEL)), (s, guard)
-        assert np.array_equal(xb[s, c.nx:], np.full(dh.GUARD, dh.SENTINEL)), (s, xb[s, c.nx:])
-        assert np.array_equal(xb[s, :c.nx].view(np.int64), inp.X[s].ravel().view(np.int64))
-        # what the config does not produce stays NaN, the rest is written
-        assert np.isnan(v).all() if not c.WV else np.isfinite(v).all()
-        assert np.isfinite(g).all() and np.isfinite(h).all()
-    err = dh.errors_of(name, lambda s: (outs[s][0] if c.WV else None, outs[s][1] if c.ND1 else None,
-                                        outs[s][2] if c.ND2 else None))
+    outs = core.assert_guards_and_nans(c, inp.X, xb, ob)
+    err = dh.errors_of(name, lambda s: core.produced(c, outs[s]))
     print(f"{name}: kernel scaled error {err}, fp64 {FP64_ERROR[name]}")
     assert set(err) == set(FP64_ERROR[name])
     for kind, e in err.items():

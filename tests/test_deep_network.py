@@ -228,7 +228,7 @@ def test_flop_count_prices_both_layers():
 @pytest.mark.parametrize("h1,h2,act1,act2", [(20, 12, "tanh", "tanh"), (16, 33, "sigmoid", "softplus")])
 def test_host_build_of_deep_room_reaches_the_oracle_optimum(h1, h2, act1, act2):
     """The generated stage functions compiled for the host (`oracle/c/gen_model.cpp`; the network
-    entries by the per-lane loops of ``symbolic._emit_deep_network``) solve the N = 8 deep room to
+    entries by the per-lane loops of ``symbolic.DeepNetwork.emit_lane``) solve the N = 8 deep room to
     the optimum of the oracle IPM over the independent NLP, whose networks torch evaluates with
     autograd derivatives (`oracle/nlps.py::_ann_torch`).  Tolerances of tests/test_gpu_ipm.py.  The
     oracle converges at tol 1e-10 for the seed of ``deep_cases.room_nn_deep`` in 8 / 8 iterations

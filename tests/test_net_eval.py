@@ -13,26 +13,17 @@ another order over at most 18 inputs / 48 hidden units, and the device exp / tan
 to a few ulp.
 """
 
-import json
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+from tests import eval_harness_core as core
 from tests import net_eval_harness as nh
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in nh.CONFIGS]
-FACTOR = 8.0
-FLOOR = 4.0 * nh.EPS
-
-with open(os.path.join(ROOT, "tests", "golden", "net_eval_fp64_error.json")) as _f:
-    FP64_ERROR = json.load(_f)
-
-
-def _bound(name, kind):
-    return max(FACTOR * FP64_ERROR[name][kind], FLOOR)
+FP64_ERROR, _bound = core.golden("net_eval")
 
 
 def test_config_tables_hit_the_edges():
@@ -88,44 +79,17 @@ def test_harness_source_compiles_for_gfx950():
 # GPU
 # ---------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def harness():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return nh.load(nh.build())
+harness = core.harness_fixture(nh)
 
 
 def run_config(lib, name):
     """Launch one config on its three input sets -> (Xback [NB, NX + GUARD], Oback [NB, NO + GUARD])."""
-    import torch
-
     c, inp = nh.BY_NAME[name], nh.inputs(name)
-    dev = torch.device("cuda:0")
-    up = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
-    X, W1T, B1, W2, b2 = up(inp.X), up(inp.W1T), up(inp.b1), up(inp.w2), up(inp.b2)
-    assert X.numel() == nh.NB * c.nx and W1T.numel() == nh.NB * c.H * c.NIN
-    assert B1.numel() == W2.numel() == nh.NB * c.H and b2.numel() == nh.NB
-    D1 = up(inp.d1, torch.int32) if c.ND1 else None
-    PW = up(inp.PW) if c.ND2 else None
-    assert PW is None or PW.numel() == nh.NB * c.ND2 * c.H
-    Xb = torch.zeros(nh.NB, c.nx + nh.GUARD, dtype=torch.float64, device=dev)
-    Ob = torch.zeros(nh.NB, c.nout + nh.GUARD, dtype=torch.float64, device=dev)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    torch.cuda.synchronize()
-    rc = getattr(lib, f"launch_{name}")(ptr(X), ptr(W1T), ptr(B1), ptr(W2), ptr(b2), ptr(D1), ptr(PW),
-                                        ptr(Xb), ptr(Ob), nh.NB)
-    torch.cuda.synchronize()
-    assert rc == 0
-    return Xb.cpu().numpy(), Ob.cpu().numpy()
-
-
-def split_outputs(c, ob):
-    """One set's LDS output array -> V [R], G [R, ND1], Hd [R, ND2], guard."""
-    R = c.R
-    v, g, h = ob[:R], ob[R:R + R * c.ND1], ob[R + R * c.ND1:c.nout]
-    return v, g.reshape(R, c.ND1), h.reshape(R, c.ND2), ob[c.nout:]
+    assert inp.W1T.size == nh.NB * c.H * c.NIN
+    assert inp.b1.size == inp.w2.size == nh.NB * c.H and inp.b2.size == nh.NB
+    assert inp.PW.size == nh.NB * c.ND2 * c.H
+    return core.launch(lib, c, nh.NB, inp.X, [inp.W1T, inp.b1, inp.w2, inp.b2, inp.d1 if c.ND1 else None,
+                                              inp.PW if c.ND2 else None])
 
 
 @pytest.mark.gpu
@@ -133,19 +97,8 @@ def split_outputs(c, ob):
 def test_eval_matches_reference(name, harness):
     c, inp = nh.BY_NAME[name], nh.inputs(name)
     xb, ob = run_config(harness, name)
-    outs = [split_outputs(c, ob[s]) for s in range(nh.NB)]
-    for s in range(nh.NB):
-        v, g, h, guard = outs[s]
-        # the guards of both LDS arrays and the LDS input are untouched
-        assert np.array_equal(guard, np.full(nh.GUARD, nh.SENTINEL)), (s, guard)
-        assert np.array_equal(xb[s, c.nx:], np.full(nh.GUARD, nh.SENTINEL)), (s, xb[s, c.nx:])
-        assert np.array_equal(xb[s, :c.nx].view(np.int64), inp.X[s].ravel().view(np.int64))
-        # what the config does not produce stays NaN (an empty G or Hd block has no room of its
-        # own: a stray write there lands in the next block or the guard), the rest is written
-        assert np.isnan(v).all() if not c.WV else np.isfinite(v).all()
-        assert np.isfinite(g).all() and np.isfinite(h).all()
-    err = nh.errors_of(name, lambda s: (outs[s][0] if c.WV else None, outs[s][1] if c.ND1 else None,
-                                        outs[s][2] if c.ND2 else None))
+    outs = core.assert_guards_and_nans(c, inp.X, xb, ob)
+    err = nh.errors_of(name, lambda s: core.produced(c, outs[s]))
     print(f"{name}: kernel scaled error {err}, fp64 {FP64_ERROR[name]}")
     assert set(err) == set(FP64_ERROR[name])
     for kind, e in err.items():

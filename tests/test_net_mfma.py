@@ -83,6 +83,28 @@ def test_network_section_follows_the_topology():
         assert any(int(c[5]) == len(d1) and int(c[1]) == n_in[nid] for c in calls)
 
 
+def test_every_table_a_kind_names_is_declared():
+    """For one network of each kind, with a gradient and a pair: every ``ANN<id>_<NAME>`` in the
+    wave call and in the lane loop is a table of ``tables()`` or, with the evaluation kind
+    appended, one of ``wave_tables()`` (``D1<kind>`` is the generator's own)."""
+    rng = np.random.default_rng(3)
+    nets = [sx.Network(rng.normal(size=(3, 5)), rng.normal(size=5), rng.normal(size=5), 0.25, "tanh"),
+            sx.RBFNetwork(rng.normal(size=(6, 3)), rng.normal(size=6), rng.uniform(0.5, 2.0, 3), rng.normal(size=3)),
+            sx.DeepNetwork(rng.normal(size=(3, 5)), rng.normal(size=5), rng.normal(size=(5, 4)), rng.normal(size=4),
+                           rng.normal(size=4), -0.5, "sigmoid", "softplus")]
+    d1, d2 = [0, 2], [(1, 0), (2, 2)]
+    for net in nets:
+        declared = {s for s, _ in net.tables()}
+        wave = declared | {"D1hess"} | {s + "hess" for s, _ in net.wave_tables(d2)}
+        call = net.wave_call("ANN7", "hess", 8, True, len(d1), len(d2), ["X", "O", "O + 8", "O + 24"])
+        lane = "\n".join(net.emit_lane("ANN7", ["x0", "x1", "x2"], True, d1, d2, "q"))
+        assert call.startswith(f"mpcx_net::{net.wave_fn}<8, 3, ") and call.endswith(", lane);")
+        used_call, used_lane = set(re.findall(r"ANN7_(\w+)", call)), set(re.findall(r"ANN7_(\w+)", lane))
+        assert used_call and used_call <= wave, (type(net).__name__, used_call - wave)
+        assert used_lane and used_lane <= declared, (type(net).__name__, used_lane - declared)
+        assert set(net.wave_pair_args) == {s for s, _ in net.wave_tables(d2)}
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
                     reason="hipcc not available")
 def test_code_object_issues_fp64_mfma(tmp_path):

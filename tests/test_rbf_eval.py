@@ -13,26 +13,17 @@ regenerate with ``python -m tests.rbf_eval_harness``), and never below a floor o
 fourth input set (every weight underflows) is only asserted finite and below 1e-290.
 """
 
-import json
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+from tests import eval_harness_core as core
 from tests import rbf_eval_harness as rh
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in rh.CONFIGS]
-FACTOR = 8.0
-FLOOR = 4.0 * rh.EPS
-
-with open(os.path.join(ROOT, "tests", "golden", "rbf_eval_fp64_error.json")) as _f:
-    FP64_ERROR = json.load(_f)
-
-
-def _bound(name, kind):
-    return max(FACTOR * FP64_ERROR[name][kind], FLOOR)
+FP64_ERROR, _bound = core.golden("rbf_eval")
 
 
 def test_config_table_hits_the_edges():
@@ -96,44 +87,17 @@ def test_harness_source_compiles_for_gfx950():
 # GPU
 # ---------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def harness():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return rh.load(rh.build())
+harness = core.harness_fixture(rh)
 
 
 def run_config(lib, name):
     """Launch one config on its four input sets -> (Xback [NB, NX + GUARD], Oback [NB, NO + GUARD])."""
-    import torch
-
     c, inp = rh.BY_NAME[name], rh.inputs(name)
-    dev = torch.device("cuda:0")
-    up = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
-    X, T, TT, A, S, SH = up(inp.X), up(inp.T), up(inp.TT), up(inp.a), up(inp.s), up(inp.t)
-    assert X.numel() == rh.NB * c.nx and T.numel() == rh.NB * c.NT * c.NIN
-    assert TT.numel() == A.numel() == rh.NB * c.NT and S.numel() == SH.numel() == rh.NB * c.NIN
-    D1 = up(inp.d1, torch.int32) if c.ND1 else None
-    P2 = up(inp.P2, torch.int32) if c.ND2 else None
-    assert P2 is None or P2.numel() == 2 * c.ND2
-    Xb = torch.zeros(rh.NB, c.nx + rh.GUARD, dtype=torch.float64, device=dev)
-    Ob = torch.zeros(rh.NB, c.nout + rh.GUARD, dtype=torch.float64, device=dev)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    torch.cuda.synchronize()
-    rc = getattr(lib, f"launch_{name}")(ptr(X), ptr(T), ptr(TT), ptr(A), ptr(S), ptr(SH), ptr(D1), ptr(P2),
-                                        ptr(Xb), ptr(Ob), rh.NB)
-    torch.cuda.synchronize()
-    assert rc == 0
-    return Xb.cpu().numpy(), Ob.cpu().numpy()
-
-
-def split_outputs(c, ob):
-    """One set's LDS output array -> V [R], G [R, ND1], Hd [R, ND2], guard."""
-    R = c.R
-    v, g, h = ob[:R], ob[R:R + R * c.ND1], ob[R + R * c.ND1:c.nout]
-    return v, g.reshape(R, c.ND1), h.reshape(R, c.ND2), ob[c.nout:]
+    assert inp.T.size == rh.NB * c.NT * c.NIN
+    assert inp.TT.size == inp.a.size == rh.NB * c.NT and inp.s.size == inp.t.size == rh.NB * c.NIN
+    assert inp.P2.size == 2 * c.ND2
+    return core.launch(lib, c, rh.NB, inp.X, [inp.T, inp.TT, inp.a, inp.s, inp.t, inp.d1 if c.ND1 else None,
+                                              inp.P2 if c.ND2 else None])
 
 
 @pytest.mark.gpu
@@ -141,21 +105,11 @@ def split_outputs(c, ob):
 def test_eval_rbf_matches_reference(name, harness):
     c, inp = rh.BY_NAME[name], rh.inputs(name)
     xb, ob = run_config(harness, name)
-    outs = [split_outputs(c, ob[s]) for s in range(rh.NB)]
-    for s in range(rh.NB):
-        v, g, h, guard = outs[s]
-        # the guards of both LDS arrays and the LDS input are untouched
-        assert np.array_equal(guard, np.full(rh.GUARD, rh.SENTINEL)), (s, guard)
-        assert np.array_equal(xb[s, c.nx:], np.full(rh.GUARD, rh.SENTINEL)), (s, xb[s, c.nx:])
-        assert np.array_equal(xb[s, :c.nx].view(np.int64), inp.X[s].ravel().view(np.int64))
-        # what the config does not produce stays NaN, the rest is written
-        assert np.isnan(v).all() if not c.WV else np.isfinite(v).all()
-        assert np.isfinite(g).all() and np.isfinite(h).all()
+    outs = core.assert_guards_and_nans(c, inp.X, xb, ob)
     # every weight underflows: finite, and nothing above 1e-290
     for part in outs[3][:3]:
         assert np.all(np.abs(part[np.isfinite(part)]) < rh.UNDERFLOW_BOUND), part
-    err = rh.errors_of(name, lambda s: (outs[s][0] if c.WV else None, outs[s][1] if c.ND1 else None,
-                                        outs[s][2] if c.ND2 else None))
+    err = rh.errors_of(name, lambda s: core.produced(c, outs[s]))
     ratio = {k: e / FP64_ERROR[name][k] for k, e in err.items()}
     print(f"{name}: kernel scaled error {err}, fp64 {FP64_ERROR[name]}, kernel/fp64 {ratio}")
     assert set(err) == set(FP64_ERROR[name])
