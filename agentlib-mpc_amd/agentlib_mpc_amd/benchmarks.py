@@ -489,6 +489,9 @@ def compile_all(verbose: bool = False):
     variants["mhe_room"] = lambda: mhe_room()
     variants["mhe_room_u"] = lambda: mhe_room(estimate="mDot")
     variants["rng_room_mpc"] = lambda: rng_room_mpc()
+    # rows on both sides of the 64-row slots of the packed slack arrays (tests/test_gpu_row_compaction.py)
+    for n_ in (9, 10, 19):
+        variants[f"one_room_n{n_}"] = lambda n_=n_: one_room(N=n_)
     from concurrent.futures import ThreadPoolExecutor
 
     probs = {name: fn()[0].problem for name, fn in variants.items()}

@@ -571,7 +571,9 @@ union LinLds {
   ParLds p;
   ParCLds c;
   double sol[N * NB];   // Newton step, block order [V, X1, lambda] per stage
-  TrialLds t;           // line-search trial point (x, scaled g)
+  TrialLds t;           // size only: the line-search trial point (x, scaled g) is reached through
+                        // trial() (below), which places it behind sol where both fit -- gL.u.t would
+                        // alias the resident step there
 };
 
 struct Lds : LdsRest {
@@ -591,6 +593,29 @@ constexpr int MIN_WAVES = (APC + 3) / 4;
 #endif
 
 __shared__ Lds gL;  // one agent per workgroup: the agent's LDS scratch
+// The Newton step (sol) and the line-search trial point side by side in the union where both fit into
+// what the union already takes for the build (its stage images are the larger members): the step then
+// stays in LDS from solve() to the acceptance instead of going through the workspace (dx, dl written
+// by the step recovery, read back by every trial and by the acceptance).  Nothing between solve() and
+// accept_step writes the union but the trial point: the evaluators read and write the trial point
+// only (the network node's buffers are not in the union), the filter and its spill list live outside
+// it, and the soft restoration step reads the step before anything is factorised again.  Where the
+// pair does not fit (or MPCX_STEP_HBM, diagnostics A/B) the trial point shares the step's bytes as
+// before.  The union itself is unchanged either way: no structure's LDS share, agents per CU or
+// stage rounds move.  The restoration phase keeps its workspace step (dx, dl).
+#ifndef MPCX_STEP_HBM
+constexpr bool STEP_RES = 8 * N * NB + sizeof(TrialLds) <= sizeof(LinLds);
+#else
+constexpr bool STEP_RES = false;
+#endif
+constexpr int TRIAL_OFF = STEP_RES ? 8 * N * NB : 0;  // bytes from the union's start
+static_assert(TRIAL_OFF + sizeof(TrialLds) <= sizeof(LinLds), "trial point inside the union");
+__device__ __forceinline__ TrialLds& trial() {
+  return *reinterpret_cast<TrialLds*>(reinterpret_cast<char*>(&gL.u) + TRIAL_OFF);
+}
+// the resident step's entries: the primal step of variable i (NX <= i < NW), the multiplier step of row c
+__device__ __forceinline__ double sol_x(int i) { return gL.u.sol[((i - NX) / NP) * NB + (i - NX) % NP]; }
+__device__ __forceinline__ double sol_l(int c) { return gL.u.sol[(c / NG) * NB + NP + c % NG]; }
 __device__ __forceinline__ KArgs* kargs() { return (KArgs*)uni64(gL.kp_bits); }
 #ifdef MPCX_WS_LDS
 __shared__ double gWS[WS_HOT];
@@ -715,6 +740,33 @@ __device__ __forceinline__ int cls_of(double lo, double hi, double sl, double su
 static_assert(2 * CS + 3 * VS <= 32, "element classes: 2 bits per constraint slot, 3 per variable slot, one word");
 __device__ __forceinline__ unsigned cls_word() { return gL.ecls[lane_now()]; }
 __device__ __forceinline__ int cls_slot(unsigned w, int sl) { return (int)((w >> (2 * sl)) & 3u); }
+// the class of an arbitrary row (cold paths: the lane does not own the row)
+__device__ __forceinline__ int cls_row(int c) { return cls_slot(gL.ecls[c & (WAVE - 1)], c / WAVE); }
+// The slack-side arrays (s, sL, sU, vL, vU, ds and the backups sr, vl0, vu0) hold only the rows that
+// have a slack -- classes 1 and 2, lb != ub -- packed in row order: an equality row never uses any of
+// them, and in a stage block equalities and inequalities interleave, so a row-indexed layout streams
+// every line for the few rows that need it (one_room: 30 of 105).  The packed index of the row in slot
+// sl of this lane is the number of slack rows below it: a ballot of the slot's classes counted over the
+// lower lanes, plus the earlier slots' (wave-uniform) counts.  Every lane of the wave calls it (no
+// divergence); a lane whose row has no slack gets the index of the next slack row (clamped to the
+// array), so its unconditional loads share lines with its neighbours' and what it loads is never used.
+// What such a lane loads is another row's entry, or -- with no slack row below the array's end -- an
+// entry no solve ever wrote: it may be a NaN or an infinity, so a phase consumes these operands only
+// under a select on the row's class (cl == 1 / cl != 0, rcp_or0(cl == 1 ...)), never in arithmetic
+// whose result is kept for a class-0 row.
+// MPCX_ROWS_FULL (diagnostics, A/B): the row index itself.
+__device__ __forceinline__ int sidx_slot(unsigned cw, int sl) {
+#ifdef MPCX_ROWS_FULL
+  const int c = lane_now() + sl * WAVE;
+  return c < M ? c : MM - 1;
+#else
+  int k = 0;
+  for (int q = 0; q < sl; ++q) k += __popcll(__ballot(cls_slot(cw, q) != 0));
+  const unsigned long long b = __ballot(cls_slot(cw, sl) != 0);
+  k += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+  return k < MM ? k : MM - 1;
+#endif
+}
 // The same for the variables (slot sl: variable lane + 64 sl): VFREE (NX <= i < NW, lo != hi),
 // VLO / VHI (finite lower / upper bound), 3 bits per slot -- the hot phases' branches on a variable's
 // bounds then do not wait for the bound loads (the compiler issued a slot's other loads only after
@@ -755,12 +807,12 @@ __device__ __forceinline__ const double* par_global() { return (const double*)gL
 
 // f and unscaled g at the trial point in LDS (xt -> gt); returns wave-summed f
 __device__ MPCX_HOT double eval_fg_lds(const Agent a) {
-  NET_PREP(gL.u.t.xt, fg);
+  NET_PREP(trial().xt, fg);
   double f = 0.0;
   for (int k = lane_now(); k < N; k += WAVE) {
     double fk = 0.0;
-    STAGE_FG((const double*)(gL.u.t.xt + k * NP), par_stage(k), par_global(), k * TS, &fk,
-             (double*)(gL.u.t.gt + k * NG), 1);
+    STAGE_FG((const double*)(trial().xt + k * NP), par_stage(k), par_global(), k * TS, &fk,
+             (double*)(trial().gt + k * NG), 1);
     f += fk;
   }
   return wsum(f);
@@ -792,10 +844,10 @@ __device__ __noinline__ void eval_gj_ws(const Agent a, const wdbl* xv, int full)
 // inlined into the kernel body: as a leaf call it saved and restored the callee-saved VGPRs
 // its generated derivative code uses on every iteration (C3 -4 %, profiles/r03/s2/var_sgpr_c3.txt)
 __device__ __attribute__((always_inline)) void eval_gj_lds(const Agent a) {
-  NET_PREP(gL.u.t.xt, gj);
+  NET_PREP(trial().xt, gj);
   const int full = gL.want_sdh;
   for (int k = lane_now(); k < N; k += WAVE)
-    STAGE_GJ((const double*)(gL.u.t.xt + k * NP), par_stage(k), par_global(), k * TS,
+    STAGE_GJ((const double*)(trial().xt + k * NP), par_stage(k), par_global(), k * TS,
              (double*)(a.sdg() + k), (double*)(a.sdj() + k), N, (const double*)(a.gs() + k * NG),
              (double*)a.lp(k), (const double*)(a.lam() + k * NG), (double*)(a.jtl() + k), full);
 }
@@ -1241,8 +1293,7 @@ __device__ __noinline__ void kkt_diagonals(const Agent a, const KKTDiag kd) {
     a.kx()[q] = (lo == hi) ? NAN : (kd.mode == LSQ ? 1.0 : a.dg(b)[off < NV ? off : LX1 + off - NV] + kd.dw);
   }
   for (int c = lane_now(); c < M; c += WAVE) {
-    const double sl = a.sL()[c], su = a.sU()[c];
-    const int cl = cls_of(a.lb()[c], a.ub()[c], sl, su);
+    const int cl = cls_row(c);
     a.kd()[c] = kd.mode == LSQ ? dual_diag_v(cl, 0.0, kd) : -a.dg(c / NG)[crow(c % NG)];
   }
   sync();
@@ -1453,24 +1504,20 @@ __device__ __forceinline__ int lblk(int i, int kind) {
   return kind == 0 ? i : (kdual(kind) ? NP + lrow(i) : NV + (i - LX1));
 }
 
-// diagonal terms (barrier Sigma + delta_w, dual diagonal) and fixed variables
+// diagonal terms of the least-squares multiplier system (the only system assembled from the strided
+// derivative arrays, local_assemble_lsq): identity on the free primal entries,
+// the dual diagonal from the row's class -- no Sigma terms, so nothing is read from the iterate or
+// from the packed slack arrays.  A Newton system never comes this way (local_assemble builds it from
+// the diagonal terms the rhs phases wrote).
 template <int GG, bool COMPACT>
-__device__ __forceinline__ void local_diagonal(const Agent a, int k, int g, ldsd* F, const KKTDiag kd,
-                                               unsigned long long fm) {
-  const wdbl* ws = a.base();
+__device__ __forceinline__ void local_diagonal_lsq(int k, int g, ldsd* F, unsigned long long fm) {
   for (int i = g; i < NLOC; i += GG) {
     const int ki = lkind(i);
     const bool prim = (ki == 0 || ki == 3);
     const bool fixd = (fm >> i) & 1ull;
-    const int vi = prim ? lvar(k, i, ki) : 0;
-    const int c = kdual(ki) ? k * NG + lrow(i) : 0;
-    const double xv = ws[O_X + vi], lo = ws[O_XL + vi], hi = ws[O_XU + vi];
-    const double zl = ws[O_ZL + vi], zu = ws[O_ZU + vi];
-    const double lbv = ws[O_LB + c], ubv = ws[O_UB + c], sv = ws[O_S + c];
-    const double sl = ws[O_SL + c], su = ws[O_SU + c], vl = ws[O_VL + c], vu = ws[O_VU + c];
     const int ii = COMPACT ? i : pko(i) + i;
-    if (prim && !fixd) F[ii] += (kd.mode == LSQ) ? 1.0 : sigma_x_v(xv, lo, hi, zl, zu) + kd.dw;
-    if (kdual(ki)) F[ii] = -dual_diag_v(cls_of(lbv, ubv, sl, su), sigma_s_v(sv, sl, su, vl, vu), kd);
+    if (prim && !fixd) F[ii] += 1.0;
+    if (kdual(ki)) F[ii] = -dual_diag_v(cls_row(k * NG + lrow(i)), 0.0, KKTDiag{0.0, 0.0, LSQ});
   }
   wsync();
 }
@@ -1509,7 +1556,8 @@ __device__ __forceinline__ double generic_entry(const Agent a, int k, int i, int
 // strided derivative arrays (least-squares multiplier system); COMPACT: the compact
 // image (static path), else the dense packed lower triangle (Bunch-Kaufman path)
 template <int GG, bool COMPACT>
-__device__ __noinline__ void local_assemble_generic(const Agent a, int k, int g, ldsd* F, const KKTDiag kd) {
+__device__ __noinline__ void local_assemble_lsq(const Agent a, int k, int g, ldsd* F) {
+  const KKTDiag kd{0.0, 0.0, LSQ};  // the mode is part of the function: no Newton system can be asked of it
   const unsigned long long fm = gL.fixm[k];
 #pragma unroll 4
   for (int t = g; t < (COMPACT ? NCPT : PKB); t += GG) {
@@ -1525,8 +1573,8 @@ __device__ __noinline__ void local_assemble_generic(const Agent a, int k, int g,
     F[t] = generic_entry(a, k, i, j, fm, kd);
   }
   wsync();
-  // pass 2: diagonal terms (barrier Sigma + delta_w, dual diagonal)
-  local_diagonal<GG, COMPACT>(a, k, g, F, kd, fm);
+  // pass 2: diagonal terms
+  local_diagonal_lsq<GG, COMPACT>(k, g, F, fm);
 }
 
 // Newton system of stage k from the compact image the evaluators wrote (stage-minor in
@@ -2316,7 +2364,7 @@ __device__ __forceinline__ Inertia factor(const Agent a, const KKTDiag kd) {
       const int slot = lane_now() % SRC, g = lane_now() / SRC, k = K0 + r * SRC + slot;
       if (g < GC && k < N) {
         ldsd* F = LDSP(L.u.c.F + slot * NCS);
-        if (kd.mode == LSQ) local_assemble_generic<GC, true>(a, k, g, F, kd);
+        if (kd.mode == LSQ) local_assemble_lsq<GC, true>(a, k, g, F);
         else local_assemble<GC, false>(a, k, g, F, kd);
       }
       wsync();
@@ -2337,7 +2385,7 @@ __device__ __forceinline__ Inertia factor(const Agent a, const KKTDiag kd) {
     ldsd* F = LDSP(L.u.c.F);
     if (!reg_asm) {
       if (lane_now() < GC) {
-        if (kd.mode == LSQ) local_assemble_generic<GC, true>(a, 0, lane_now(), F, kd);
+        if (kd.mode == LSQ) local_assemble_lsq<GC, true>(a, 0, lane_now(), F);
         else local_assemble<GC, false>(a, 0, lane_now(), F, kd);
       }
       wsync();
@@ -2368,7 +2416,7 @@ __device__ __forceinline__ Inertia factor(const Agent a, const KKTDiag kd) {
           ldsd* F = LDSP(L.u.p.F + slot * PKS);
           ldsi* perm = LDSI(L.u.p.perm + slot * NI);
           for (int i = g; i < NI; i += G) perm[i] = i;
-          if (kd.mode == LSQ) local_assemble_generic<G, false>(a, k, g, F, kd);
+          if (kd.mode == LSQ) local_assemble_lsq<G, false>(a, k, g, F);
           else local_assemble<G, true>(a, k, g, F, kd);
         }
       }
@@ -2604,30 +2652,36 @@ __device__ __noinline__ Scal init_agent(const Agent a, int agent) {
     sc.square = wsumi(nfree) == wsumi(neq);
   }
   sync();
-  for (int c = lane; c < M; c += WAVE) {
-    const double gsc = a.gs()[c];
-    a.gv()[c] *= gsc;
-    const double lo = a.lb()[c], hi = a.ub()[c];
-    if (lo == hi) {
-      a.sL()[c] = gsc * lo; a.sU()[c] = gsc * hi; a.s()[c] = gsc * lo;
-      a.vL()[c] = 0.0; a.vU()[c] = 0.0;
-    } else {
-      const double sl = isfin(lo) ? relax_lo(gsc * lo, o.bound_relax_factor) : -INFINITY;
-      const double su = isfin(hi) ? relax_hi(gsc * hi, o.bound_relax_factor) : INFINITY;
-      a.sL()[c] = sl; a.sU()[c] = su;
-      a.s()[c] = push_into(a.gv()[c], sl, su, o.bound_push, o.bound_frac);
-      a.vL()[c] = isfin(sl) ? o.bound_mult_init_val : 0.0;
-      a.vU()[c] = isfin(su) ? o.bound_mult_init_val : 0.0;
-    }
-    a.lam()[c] = 0.0;
-  }
-  {  // the rows' classes for the hot phases (this lane wrote its rows' bounds above)
-    unsigned w = 0u;
+  {
+    // the rows' classes first (equality from lb == ub, inequality against free from the relaxed bounds,
+    // kept in registers): the packed index of a slack row counts the classes of the rows below it
+    unsigned cw = 0u;
+    double slv[CS], suv[CS];
+#pragma unroll
     for (int sl = 0; sl < CS; ++sl) {
       const int c = lane + sl * WAVE;
-      if (c < M) w |= (unsigned)cls_of(a.lb()[c], a.ub()[c], a.sL()[c], a.sU()[c]) << (2 * sl);
+      slv[sl] = -INFINITY; suv[sl] = INFINITY;
+      if (c < M) {
+        const double gsc = a.gs()[c], lo = a.lb()[c], hi = a.ub()[c];
+        if (isfin(lo)) slv[sl] = relax_lo(gsc * lo, o.bound_relax_factor);
+        if (isfin(hi)) suv[sl] = relax_hi(gsc * hi, o.bound_relax_factor);
+        cw |= (unsigned)cls_of(lo, hi, slv[sl], suv[sl]) << (2 * sl);
+      }
     }
-    gL.ecls[lane] |= w;
+    gL.ecls[lane] |= cw;  // for the hot phases
+#pragma unroll
+    for (int sl = 0; sl < CS; ++sl) {
+      const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+      if (c >= M) continue;
+      const double gvs = a.gv()[c] * a.gs()[c];
+      a.gv()[c] = gvs;
+      a.lam()[c] = 0.0;
+      if (cls_slot(cw, sl) == 0) continue;  // an equality row has no slack: nothing of it in the packed arrays
+      a.sL()[q] = slv[sl]; a.sU()[q] = suv[sl];
+      a.s()[q] = push_into(gvs, slv[sl], suv[sl], o.bound_push, o.bound_frac);
+      a.vL()[q] = isfin(slv[sl]) ? o.bound_mult_init_val : 0.0;
+      a.vU()[q] = isfin(suv[sl]) ? o.bound_mult_init_val : 0.0;
+    }
   }
   sync();
   eval_gj_ws(a, a.x(), 1);
@@ -2638,9 +2692,12 @@ __device__ __noinline__ Scal init_agent(const Agent a, int agent) {
 // sum |c(x) - s| (scaled) at the current point
 __device__ __noinline__ double theta_now(const Agent a) {
   double t = 0.0;
-  for (int c = lane_now(); c < M; c += WAVE) {
-    const int cl = cls_of(a.lb()[c], a.ub()[c], a.sL()[c], a.sU()[c]);
-    const double cv = (cl == 0) ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[c];
+  const int lane = lane_now();
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+    if (c >= M) continue;
+    const double cv = (cls_slot(cw, sl) == 0) ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[q];
     t += fabs(cv);
   }
   return wsum(t);
@@ -2655,10 +2712,10 @@ __device__ __noinline__ void rhs_dual(const Agent a, double mu, double dw, doubl
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     const bool on = c < M;
-    const int cc = on ? c : 0;
-    const double lbv = a.lb()[cc], slo = a.sL()[cc], sup = a.sU()[cc];
-    const double gvv = a.gv()[cc], gsc = a.gs()[cc], sv = a.s()[cc], lm = a.lam()[cc];
-    const double vl = a.vL()[cc], vu = a.vU()[cc];
+    const int cc = on ? c : 0, q = sidx_slot(cw, sl);
+    const double lbv = a.lb()[cc], slo = a.sL()[q], sup = a.sU()[q];
+    const double gvv = a.gv()[cc], gsc = a.gs()[cc], sv = a.s()[q], lm = a.lam()[cc];
+    const double vl = a.vL()[q], vu = a.vU()[q];
     if (on) {
       const int cl = cls_slot(cw, sl);
       double rr;
@@ -2693,9 +2750,11 @@ __device__ __noinline__ void ls_mult_rhs(const Agent a, double obj_scale) {
     const double r = (a.xL()[i] == a.xU()[i]) ? 0.0 : -(obj_scale * acc_grad(a, i) - a.zL()[i] + a.zU()[i]);
     a.rhs((i - NX) / NP)[(i - NX) % NP] = r;
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const int cl = cls_of(a.lb()[c], a.ub()[c], a.sL()[c], a.sU()[c]);
-    a.rhs(c / NG)[NP + c % NG] = (cl == 1) ? a.vL()[c] - a.vU()[c] : 0.0;
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+    if (c >= M) continue;
+    a.rhs(c / NG)[NP + c % NG] = (cls_slot(cw, sl) == 1) ? a.vL()[q] - a.vU()[q] : 0.0;
   }
   sync();
 }
@@ -2765,10 +2824,13 @@ constexpr double LN2 = 0.6931471805599453;
 // full step from the Newton solution (LDS) + fraction-to-the-boundary step sizes + constraint
 // violation at the current point; the barrier sum too unless the caller passes the cached one
 // (bar_cached: the current point is the last accepted trial point, whose logs the line search
-// summed -- the logs were a fifth of this phase's instructions)
+// summed -- the logs were a fifth of this phase's instructions); theta_cached: the same for the
+// constraint violation, summed by that trial from the same values in the same lane order
+// (KState::ls.tr.theta, untouched until the next line search) -- gv, gs and lb are then not loaded
 __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, double dw, double obj_scale,
-                                          int bar_cached) {
+                                          int bar_cached, int theta_cached_v) {
   const int lane = lane_now();
+  const int theta_cached = __builtin_amdgcn_readfirstlane(theta_cached_v);  // wave-uniform: a scalar branch
   RatioMin ra, rz;
   LogSum lb;
   double gphid = 0.0, theta = 0.0;
@@ -2792,7 +2854,7 @@ __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, 
     const unsigned vb = vcls_slot(vw, sl);
     const bool free_ = (vb & VFREE) != 0u;
     const double d = free_ ? sx[sl] : 0.0;
-    a.dx()[i] = d;
+    if constexpr (!STEP_RES) a.dx()[i] = d;
     if (!free_) continue;
     double gphi = obj_scale * gr[sl];
     if (vb & VLO) {
@@ -2816,12 +2878,17 @@ __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, 
   // the constraints' operands: a second batch (both at once would need more registers than a leaf
   // phase has without saving callee-saved ones: 22 scratch saves and restores per call, C3 +4 %, r06/s5)
   double lbv[CS], slo[CS], sup[CS], sv[CS], lm[CS], vl[CS], vu[CS], gvv[CS], gsc[CS], dlam[CS];
+  int sq[CS];
 #pragma unroll
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     const int cc = c < M ? c : 0;
-    lbv[sl] = a.lb()[cc]; slo[sl] = a.sL()[cc]; sup[sl] = a.sU()[cc]; sv[sl] = a.s()[cc]; lm[sl] = a.lam()[cc];
-    vl[sl] = a.vL()[cc]; vu[sl] = a.vU()[cc]; gvv[sl] = a.gv()[cc]; gsc[sl] = a.gs()[cc];
+    sq[sl] = sidx_slot(cw, sl);
+    slo[sl] = a.sL()[sq[sl]]; sup[sl] = a.sU()[sq[sl]]; sv[sl] = a.s()[sq[sl]]; lm[sl] = a.lam()[cc];
+    vl[sl] = a.vL()[sq[sl]]; vu[sl] = a.vU()[sq[sl]];
+    // theta_cached: the accepted trial summed the same terms (line_search), so its operands stay unloaded
+    lbv[sl] = 0.0; gvv[sl] = 0.0; gsc[sl] = 0.0;
+    if (!theta_cached) { lbv[sl] = a.lb()[cc]; gvv[sl] = a.gv()[cc]; gsc[sl] = a.gs()[cc]; }
     dlam[sl] = gL.u.sol[(cc / NG) * NB + NP + cc % NG];
   }
 #pragma unroll
@@ -2833,7 +2900,7 @@ __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, 
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     if (c >= M) continue;
-    a.dl()[c] = dlam[sl];
+    if constexpr (!STEP_RES) a.dl()[c] = dlam[sl];
     const int cl = cls_slot(cw, sl);
     theta += fabs((cl == 0) ? gvv[sl] - gsc[sl] * lbv[sl] : gvv[sl] - sv[sl]);
     double dsv = 0.0;
@@ -2860,13 +2927,13 @@ __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, 
         if (!bar_cached) lb.add(s_u);
       }
     }
-    a.ds()[c] = dsv;
+    if (cl != 0) a.ds()[sq[sl]] = dsv;
   }
   StepInfo st;
   st.amax = wmin(ra.value());
   st.az = wmin(rz.value());
   st.gphid = wsum(gphid);
-  st.theta = wsum(theta);
+  st.theta = theta_cached ? gL.ks.ls.tr.theta : wsum(theta);
   st.barrier = bar_cached ? gL.ks.bar_val : wsum(log(lb.m) + lb.e * LN2);
   return st;
 }
@@ -2927,7 +2994,10 @@ __device__ MPCX_HOT void line_search(const Agent a) {
 #pragma unroll
       for (int sl = 0; sl < VS; ++sl) {
         const int i = lane + sl * WAVE, ii = i < NW ? i : 0;
-        lo[sl] = a.xL()[ii]; hi[sl] = a.xU()[ii]; xv[sl] = a.x()[ii]; dx[sl] = a.dx()[ii];
+        lo[sl] = a.xL()[ii]; hi[sl] = a.xU()[ii]; xv[sl] = a.x()[ii];
+        // the step: resident (the select recover_step applies: 0 for a fixed variable), or its dx
+        if constexpr (STEP_RES) dx[sl] = (vcls_slot(vw, sl) & VFREE) ? sol_x(ii >= NX ? ii : NX) : 0.0;
+        else dx[sl] = a.dx()[ii];
       }
 #pragma unroll
       for (int sl = 0; sl < VS; ++sl) { MPCX_PIN(lo[sl]); MPCX_PIN(hi[sl]); MPCX_PIN(xv[sl]); MPCX_PIN(dx[sl]); }
@@ -2937,7 +3007,7 @@ __device__ MPCX_HOT void line_search(const Agent a) {
         if (i < NW) {
           const unsigned vb = vcls_slot(vw, sl);
           const double xt = xv[sl] + alpha * dx[sl];
-          gL.u.t.xt[i] = xt;
+          trial().xt[i] = xt;
           if (vb & VFREE) {
             if (vb & VLO) bx.add(xt - lo[sl]);
             if (vb & VHI) bx.add(hi[sl] - xt);
@@ -2960,9 +3030,9 @@ __device__ MPCX_HOT void line_search(const Agent a) {
     double gsv[CS], lbv[CS], slv[CS], suv[CS], sv[CS], dsv[CS];  // loaded first, one batch (MPCX_PIN)
 #pragma unroll
     for (int sl = 0; sl < CS; ++sl) {
-      const int c = lane + sl * WAVE, cc = c < M ? c : 0;
-      gsv[sl] = a.gs()[cc]; lbv[sl] = a.lb()[cc]; slv[sl] = a.sL()[cc]; suv[sl] = a.sU()[cc];
-      sv[sl] = a.s()[cc]; dsv[sl] = a.ds()[cc];
+      const int c = lane + sl * WAVE, cc = c < M ? c : 0, q = sidx_slot(cw, sl);
+      gsv[sl] = a.gs()[cc]; lbv[sl] = a.lb()[cc]; slv[sl] = a.sL()[q]; suv[sl] = a.sU()[q];
+      sv[sl] = a.s()[q]; dsv[sl] = a.ds()[q];
     }
 #pragma unroll
     for (int sl = 0; sl < CS; ++sl) {
@@ -2973,8 +3043,8 @@ __device__ MPCX_HOT void line_search(const Agent a) {
       const int c = lane + sl * WAVE;
       if (c < M) {
         const int cl = cls_slot(cw, sl);
-        const double gt = gL.u.t.gt[c] * gsv[sl];
-        gL.u.t.gt[c] = gt;
+        const double gt = trial().gt[c] * gsv[sl];
+        trial().gt[c] = gt;
         const double st = sv[sl] + alpha * dsv[sl];
         th += fabs(cl == 0 ? gt - gsv[sl] * lbv[sl] : gt - st);
         if (cl == 1) {
@@ -3027,6 +3097,8 @@ __device__ MPCX_HOT void line_search(const Agent a) {
 }
 
 // take the last trial point (xt, gt in LDS) and the multiplier steps
+// RES: the step is the resident Newton solution (STEP_RES; the restoration phase passes its workspace step)
+template <bool RES>
 __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, double mu, double alpha, double az) {
   const int lane = lane_now();
   const double ksm = kappa_sigma * mu, mks = mu * MPCX_RCP(kappa_sigma);  // the kappa_sigma safeguard's bounds x s
@@ -3037,9 +3109,11 @@ __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, do
   for (int sl = 0; sl < VS; ++sl) {
     const int i = lane + sl * WAVE;
     const int ii = (i >= NX && i < NW) ? i : NX;
-    lo[sl] = a.xL()[ii]; hi[sl] = a.xU()[ii]; xold[sl] = a.x()[ii]; dx[sl] = a.dx()[ii];
+    lo[sl] = a.xL()[ii]; hi[sl] = a.xU()[ii]; xold[sl] = a.x()[ii];
+    if constexpr (RES) dx[sl] = sol_x(ii);  // used by free variables only (VFREE below)
+    else dx[sl] = a.dx()[ii];
     zl[sl] = a.zL()[ii]; zu[sl] = a.zU()[ii];
-    xn[sl] = gL.u.t.xt[ii];
+    xn[sl] = trial().xt[ii];
   }
 #pragma unroll
   for (int sl = 0; sl < VS; ++sl) {
@@ -3066,13 +3140,17 @@ __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, do
   }
   // the constraints' operands: a second batch (register budget of a leaf phase, see recover_step)
   double slo[CS], sup[CS], lm[CS], dl[CS], sold[CS], dsv[CS], vl[CS], vu[CS], gt[CS];
+  int sq[CS];
 #pragma unroll
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     const int cc = c < M ? c : 0;
-    slo[sl] = a.sL()[cc]; sup[sl] = a.sU()[cc]; lm[sl] = a.lam()[cc]; dl[sl] = a.dl()[cc]; sold[sl] = a.s()[cc];
-    dsv[sl] = a.ds()[cc]; vl[sl] = a.vL()[cc]; vu[sl] = a.vU()[cc];
-    gt[sl] = gL.u.t.gt[cc];
+    sq[sl] = sidx_slot(cw, sl);
+    slo[sl] = a.sL()[sq[sl]]; sup[sl] = a.sU()[sq[sl]]; lm[sl] = a.lam()[cc]; sold[sl] = a.s()[sq[sl]];
+    if constexpr (RES) dl[sl] = sol_l(cc);
+    else dl[sl] = a.dl()[cc];
+    dsv[sl] = a.ds()[sq[sl]]; vl[sl] = a.vL()[sq[sl]]; vu[sl] = a.vU()[sq[sl]];
+    gt[sl] = trial().gt[cc];
   }
 #pragma unroll
   for (int sl = 0; sl < CS; ++sl) {
@@ -3085,20 +3163,22 @@ __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, do
     if (c >= M) continue;
     a.lam()[c] = lm[sl] + alpha * dl[sl];
     a.gv()[c] = gt[sl];
+    const int cl = cls_slot(cw, sl);
+    if (cl == 0) continue;  // no slack
     const double sn = sold[sl] + alpha * dsv[sl];
-    a.s()[c] = sn;
-    if (cls_slot(cw, sl) != 1) continue;
+    a.s()[sq[sl]] = sn;
+    if (cl != 1) continue;
     if (isfin(slo[sl])) {
       const double r0 = MPCX_RCP(sold[sl] - slo[sl]);
       const double dv = mu * r0 - vl[sl] - (vl[sl] * r0) * dsv[sl];
       const double vn = vl[sl] + az * dv, rn = MPCX_RCP(sn - slo[sl]);
-      a.vL()[c] = fmax(fmin(vn, ksm * rn), mks * rn);
+      a.vL()[sq[sl]] = fmax(fmin(vn, ksm * rn), mks * rn);
     }
     if (isfin(sup[sl])) {
       const double r0 = MPCX_RCP(sup[sl] - sold[sl]);
       const double dv = mu * r0 - vu[sl] + (vu[sl] * r0) * dsv[sl];
       const double vn = vu[sl] + az * dv, rn = MPCX_RCP(sup[sl] - sn);
-      a.vU()[c] = fmax(fmin(vn, ksm * rn), mks * rn);
+      a.vU()[sq[sl]] = fmax(fmin(vn, ksm * rn), mks * rn);
     }
   }
 }
@@ -3156,9 +3236,9 @@ __device__ __attribute__((always_inline)) int iter_head(const Agent a) {
 #pragma unroll
     for (int sl = 0; sl < CS; ++sl) {
       const int c = lane + sl * WAVE;
-      const int cc = c < M ? c : 0;
-      lb_[sl] = a.lb()[cc]; sl_[sl] = a.sL()[cc]; su_[sl] = a.sU()[cc]; gs_[sl] = a.gs()[cc]; lm_[sl] = a.lam()[cc];
-      gv_[sl] = a.gv()[cc]; sv_[sl] = a.s()[cc]; vl_[sl] = a.vL()[cc]; vu_[sl] = a.vU()[cc];
+      const int cc = c < M ? c : 0, q = sidx_slot(cw, sl);
+      lb_[sl] = a.lb()[cc]; sl_[sl] = a.sL()[q]; su_[sl] = a.sU()[q]; gs_[sl] = a.gs()[cc]; lm_[sl] = a.lam()[cc];
+      gv_[sl] = a.gv()[cc]; sv_[sl] = a.s()[q]; vl_[sl] = a.vL()[q]; vu_[sl] = a.vU()[q];
     }
 #pragma unroll
     for (int sl = 0; sl < VS; ++sl) {
@@ -3360,13 +3440,15 @@ __device__ __noinline__ double pd_error(const Agent a, double mu, double obj_sca
     if (isfin(lo)) e += fabs((xv - lo) * zl - mu);
     if (isfin(hi)) e += fabs((hi - xv) * zu - mu);
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const double lbv = a.lb()[c], ubv = a.ub()[c], slo = a.sL()[c], sup = a.sU()[c];
-    const int cl = cls_of(lbv, ubv, slo, sup);
-    const double gvv = a.gv()[c], sv = a.s()[c];
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    const double lbv = a.lb()[c], slo = a.sL()[q], sup = a.sU()[q];
+    const double gvv = a.gv()[c], sv = a.s()[q];
     e += fabs(cl == 0 ? gvv - a.gs()[c] * lbv : gvv - sv);
     if (cl == 1) {
-      const double vl = a.vL()[c], vu = a.vU()[c];
+      const double vl = a.vL()[q], vu = a.vU()[q];
       e += fabs(-a.lam()[c] - vl + vu);
       if (isfin(slo)) e += fabs((sv - slo) * vl - mu);
       if (isfin(sup)) e += fabs((sup - sv) * vu - mu);
@@ -3382,6 +3464,8 @@ __device__ __noinline__ void iterate_copy(const Agent a, int to_backup) {
     if (to_backup) { a.xr()[i] = a.x()[i]; a.zl0()[i] = a.zL()[i]; a.zu0()[i] = a.zU()[i]; }
     else { a.x()[i] = a.xr()[i]; a.zL()[i] = a.zl0()[i]; a.zU()[i] = a.zu0()[i]; }
   }
+  // the slack-side arrays and their backups are packed alike: copied up to the row capacity, whatever
+  // the number of slack rows (what lies past it is never used)
   for (int c = lane; c < M; c += WAVE) {
     if (to_backup) {
       a.sr()[c] = a.s()[c]; a.lr()[c] = a.lam()[c]; a.gvr()[c] = a.gv()[c];
@@ -3401,20 +3485,24 @@ __device__ __noinline__ void soft_apply(const Agent a, double mu, double alpha) 
   for (int i = NX + lane; i < NW; i += WAVE) {
     const double lo = a.xL()[i], hi = a.xU()[i];
     if (lo == hi) continue;
-    const double xold = a.x()[i], d = a.dx()[i];
-    a.x()[i] = gL.u.t.xt[i];
+    const double xold = a.x()[i], d = STEP_RES ? sol_x(i) : a.dx()[i];
+    a.x()[i] = trial().xt[i];
     if (isfin(lo)) { const double zl = a.zL()[i], sl0 = xold - lo; a.zL()[i] = zl + alpha * (mu / sl0 - zl - (zl / sl0) * d); }
     if (isfin(hi)) { const double zu = a.zU()[i], su0 = hi - xold; a.zU()[i] = zu + alpha * (mu / su0 - zu + (zu / su0) * d); }
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const double lbv = a.lb()[c], ubv = a.ub()[c], slo = a.sL()[c], sup = a.sU()[c];
-    const double sold = a.s()[c], dsv = a.ds()[c];
-    a.lam()[c] += alpha * a.dl()[c];
-    a.gv()[c] = gL.u.t.gt[c];
-    a.s()[c] = sold + alpha * dsv;
-    if (cls_of(lbv, ubv, slo, sup) != 1) continue;
-    if (isfin(slo)) { const double vl = a.vL()[c], s0 = sold - slo; a.vL()[c] = vl + alpha * (mu / s0 - vl - (vl / s0) * dsv); }
-    if (isfin(sup)) { const double vu = a.vU()[c], s0 = sup - sold; a.vU()[c] = vu + alpha * (mu / s0 - vu + (vu / s0) * dsv); }
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    a.lam()[c] += alpha * (STEP_RES ? sol_l(c) : a.dl()[c]);
+    a.gv()[c] = trial().gt[c];
+    if (cl == 0) continue;
+    const double slo = a.sL()[q], sup = a.sU()[q];
+    const double sold = a.s()[q], dsv = a.ds()[q];
+    a.s()[q] = sold + alpha * dsv;
+    if (cl != 1) continue;
+    if (isfin(slo)) { const double vl = a.vL()[q], s0 = sold - slo; a.vL()[q] = vl + alpha * (mu / s0 - vl - (vl / s0) * dsv); }
+    if (isfin(sup)) { const double vu = a.vU()[q], s0 = sup - sold; a.vU()[q] = vu + alpha * (mu / s0 - vu + (vu / s0) * dsv); }
   }
   sync();
 }
@@ -3428,11 +3516,13 @@ __device__ __noinline__ void sigma_clip(const Agent a, double kappa_sigma, doubl
     if (isfin(lo)) { const double s_l = xv - lo; a.zL()[i] = fmax(fmin(a.zL()[i], kappa_sigma * mu / s_l), mu / (kappa_sigma * s_l)); }
     if (isfin(hi)) { const double s_u = hi - xv; a.zU()[i] = fmax(fmin(a.zU()[i], kappa_sigma * mu / s_u), mu / (kappa_sigma * s_u)); }
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const double slo = a.sL()[c], sup = a.sU()[c], sv = a.s()[c];
-    if (cls_of(a.lb()[c], a.ub()[c], slo, sup) != 1) continue;
-    if (isfin(slo)) { const double s_l = sv - slo; a.vL()[c] = fmax(fmin(a.vL()[c], kappa_sigma * mu / s_l), mu / (kappa_sigma * s_l)); }
-    if (isfin(sup)) { const double s_u = sup - sv; a.vU()[c] = fmax(fmin(a.vU()[c], kappa_sigma * mu / s_u), mu / (kappa_sigma * s_u)); }
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+    if (c >= M || cls_slot(cw, sl) != 1) continue;
+    const double slo = a.sL()[q], sup = a.sU()[q], sv = a.s()[q];
+    if (isfin(slo)) { const double s_l = sv - slo; a.vL()[q] = fmax(fmin(a.vL()[q], kappa_sigma * mu / s_l), mu / (kappa_sigma * s_l)); }
+    if (isfin(sup)) { const double s_u = sup - sv; a.vU()[q] = fmax(fmin(a.vU()[q], kappa_sigma * mu / s_u), mu / (kappa_sigma * s_u)); }
   }
   sync();
 }
@@ -3578,9 +3668,11 @@ __device__ __noinline__ void resto_start(const Agent a) {
   K.mu0 = K.mu; K.tau0 = K.tau; K.dw_last0 = K.dw_last; K.acc0 = K.acc;
   K.fo = K.fx;
   double cmax = 0.0;
-  for (int c = lane; c < M; c += WAVE) {
-    const int cl = cls_of(a.lb()[c], a.ub()[c], a.sL()[c], a.sU()[c]);
-    cmax = fmax(cmax, fabs(cl == 0 ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[c]));
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    cmax = fmax(cmax, fabs(cl == 0 ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[q]));
   }
   const double mu_r = fmax(K.mu, wmax(cmax));
   double pn = 0.0, th = 0.0;
@@ -3593,9 +3685,10 @@ __device__ __noinline__ void resto_start(const Agent a) {
     a.zU()[i] = fmin(zu, RESTO_RHO);
     nfree += (i >= NX && a.xL()[i] != a.xU()[i]) ? 1 : 0;
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const int cl = cls_of(a.lb()[c], a.ub()[c], a.sL()[c], a.sU()[c]);
-    const double cv = cl == 0 ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[c];
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, k = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    const double cv = cl == 0 ? a.gv()[c] - a.gs()[c] * a.lb()[c] : a.gv()[c] - a.s()[k];
     // p, n solving the restoration problem's complementarity at its start (W&B 2006, eq. 33)
     const double q = (mu_r - RESTO_RHO * cv) / (2.0 * RESTO_RHO);
     const double nv = q + sqrt(q * q + mu_r * cv / (2.0 * RESTO_RHO));
@@ -3604,13 +3697,14 @@ __device__ __noinline__ void resto_start(const Agent a) {
     a.rzp()[c] = mu_r / pv; a.rzn()[c] = mu_r / nv;
     pn += pv + nv;
     th += fabs(cv - pv + nv);
-    a.sr()[c] = a.s()[c];
-    const double vl = a.vL()[c], vu = a.vU()[c];
-    a.vl0()[c] = vl; a.vu0()[c] = vu;
-    a.vL()[c] = fmin(vl, RESTO_RHO);
-    a.vU()[c] = fmin(vu, RESTO_RHO);
     a.lam()[c] = 0.0;
     neq += cl == 0 ? 1 : 0;
+    if (cl == 0) continue;  // no slack: nothing of the row in the packed arrays and their backups
+    a.sr()[k] = a.s()[k];
+    const double vl = a.vL()[k], vu = a.vU()[k];
+    a.vl0()[k] = vl; a.vu0()[k] = vu;
+    a.vL()[k] = fmin(vl, RESTO_RHO);
+    a.vU()[k] = fmin(vu, RESTO_RHO);
   }
   pn = wsum(pn);
   th = wsum(th);
@@ -3623,9 +3717,11 @@ __device__ __noinline__ void resto_start(const Agent a) {
       if (isfin(lo)) mxl = fmin(mxl, xv - lo);
       if (isfin(hi)) mxu = fmin(mxu, hi - xv);
     }
-    for (int c = lane; c < M; c += WAVE) {
-      const double slo = a.sL()[c], sup = a.sU()[c], sv = a.s()[c];
-      if (cls_of(a.lb()[c], a.ub()[c], slo, sup) == 1) {
+    for (int sl = 0; sl < CS; ++sl) {
+      const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+      if (c >= M) continue;
+      const double slo = a.sL()[q], sup = a.sU()[q], sv = a.s()[q];
+      if (cls_slot(cw, sl) == 1) {
         if (isfin(slo)) msl = fmin(msl, sv - slo);
         if (isfin(sup)) msu = fmin(msu, sup - sv);
       }
@@ -3672,12 +3768,15 @@ __device__ __noinline__ void resto_return(const Agent a) {
     if (isfin(lo)) { const double z0 = a.zl0()[i], dz = (mu0 - z0 * (xv - lo)) / (x0 - lo); if (dz < 0) ad = fmin(ad, -tau0 * z0 / dz); }
     if (isfin(hi)) { const double z0 = a.zu0()[i], dz = (mu0 - z0 * (hi - xv)) / (hi - x0); if (dz < 0) ad = fmin(ad, -tau0 * z0 / dz); }
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const double slo = a.sL()[c], sup = a.sU()[c];
-    if (cls_of(a.lb()[c], a.ub()[c], slo, sup) != 1) continue;
-    const double sv = a.s()[c], s0 = a.sr()[c];
-    if (isfin(slo)) { const double v0 = a.vl0()[c], dv = (mu0 - v0 * (sv - slo)) / (s0 - slo); if (dv < 0) ad = fmin(ad, -tau0 * v0 / dv); }
-    if (isfin(sup)) { const double v0 = a.vu0()[c], dv = (mu0 - v0 * (sup - sv)) / (sup - s0); if (dv < 0) ad = fmin(ad, -tau0 * v0 / dv); }
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    if (cl != 1) continue;
+    const double slo = a.sL()[q], sup = a.sU()[q];
+    const double sv = a.s()[q], s0 = a.sr()[q];
+    if (isfin(slo)) { const double v0 = a.vl0()[q], dv = (mu0 - v0 * (sv - slo)) / (s0 - slo); if (dv < 0) ad = fmin(ad, -tau0 * v0 / dv); }
+    if (isfin(sup)) { const double v0 = a.vu0()[q], dv = (mu0 - v0 * (sup - sv)) / (sup - s0); if (dv < 0) ad = fmin(ad, -tau0 * v0 / dv); }
   }
   ad = wmin(ad);
   double zmax = 0.0;
@@ -3688,13 +3787,15 @@ __device__ __noinline__ void resto_return(const Agent a) {
     if (isfin(lo)) { const double z0 = a.zl0()[i], z = z0 + ad * (mu0 - z0 * (xv - lo)) / (x0 - lo); a.zL()[i] = z; zmax = fmax(zmax, fabs(z)); }
     if (isfin(hi)) { const double z0 = a.zu0()[i], z = z0 + ad * (mu0 - z0 * (hi - xv)) / (hi - x0); a.zU()[i] = z; zmax = fmax(zmax, fabs(z)); }
   }
-  for (int c = lane; c < M; c += WAVE) {
-    const double slo = a.sL()[c], sup = a.sU()[c];
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
     a.lam()[c] = 0.0;  // constr_mult_reset_threshold = 0: constraint multipliers restart at zero
-    if (cls_of(a.lb()[c], a.ub()[c], slo, sup) != 1) continue;
-    const double sv = a.s()[c], s0 = a.sr()[c];
-    if (isfin(slo)) { const double v0 = a.vl0()[c], v = v0 + ad * (mu0 - v0 * (sv - slo)) / (s0 - slo); a.vL()[c] = v; zmax = fmax(zmax, fabs(v)); }
-    if (isfin(sup)) { const double v0 = a.vu0()[c], v = v0 + ad * (mu0 - v0 * (sup - sv)) / (sup - s0); a.vU()[c] = v; zmax = fmax(zmax, fabs(v)); }
+    if (cl != 1) continue;
+    const double slo = a.sL()[q], sup = a.sU()[q];
+    const double sv = a.s()[q], s0 = a.sr()[q];
+    if (isfin(slo)) { const double v0 = a.vl0()[q], v = v0 + ad * (mu0 - v0 * (sv - slo)) / (s0 - slo); a.vL()[q] = v; zmax = fmax(zmax, fabs(v)); }
+    if (isfin(sup)) { const double v0 = a.vu0()[q], v = v0 + ad * (mu0 - v0 * (sup - sv)) / (sup - s0); a.vU()[q] = v; zmax = fmax(zmax, fabs(v)); }
   }
   zmax = wmax(zmax);
   if (zmax > BOUND_MULT_RESET) {
@@ -3704,11 +3805,11 @@ __device__ __noinline__ void resto_return(const Agent a) {
       a.zL()[i] = isfin(lo) ? 1.0 : 0.0;
       a.zU()[i] = isfin(hi) ? 1.0 : 0.0;
     }
-    for (int c = lane; c < M; c += WAVE) {
-      const double slo = a.sL()[c], sup = a.sU()[c];
-      if (cls_of(a.lb()[c], a.ub()[c], slo, sup) != 1) continue;
-      a.vL()[c] = isfin(slo) ? 1.0 : 0.0;
-      a.vU()[c] = isfin(sup) ? 1.0 : 0.0;
+    for (int sl = 0; sl < CS; ++sl) {
+      const int c = lane + sl * WAVE, q = sidx_slot(cw, sl);
+      if (c >= M || cls_slot(cw, sl) != 1) continue;
+      a.vL()[q] = isfin(a.sL()[q]) ? 1.0 : 0.0;
+      a.vU()[q] = isfin(a.sU()[q]) ? 1.0 : 0.0;
     }
   }
   const int nfilt = K.nfilt0;
@@ -3764,15 +3865,14 @@ __device__ __noinline__ int iter_head_resto(const Agent a) {
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     const int cc = c < M ? c : 0;
-    const double lbv = a.lb()[cc], ubv = a.ub()[cc], slo = a.sL()[cc], sup = a.sU()[cc];
-    const double gsc = a.gs()[cc], gvv = a.gv()[cc], sv = a.s()[cc], lm = a.lam()[cc];
-    const double vl = a.vL()[cc], vu = a.vU()[cc];
+    const unsigned cw = cls_word();
+    const int q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    const double lbv = a.lb()[cc], slo = a.sL()[q], sup = a.sU()[q];
+    const double gsc = a.gs()[cc], gvv = a.gv()[cc], sv = a.s()[q], lm = a.lam()[cc];
+    const double vl = a.vL()[q], vu = a.vU()[q];
     const double pv = a.rp()[cc], nv = a.rn()[cc], zp = a.rzp()[cc], zn = a.rzn()[cc];
-    const int cl = cls_of(lbv, ubv, slo, sup);
     const double co = (cl == 0) ? gvv - gsc * lbv : gvv - sv;   // original residual
     const double cr = co - pv + nv;                               // restoration residual
-    const double sg = sigma_s_v(sv, slo, sup, vl, vu);
-    const double sgp = zp / pv, sgn = zn / nv;
     if (c < M) {
       tho += fabs(co);
       pmax = fmax(pmax, fabs(cr));
@@ -3886,13 +3986,15 @@ __device__ __noinline__ int iter_head_resto(const Agent a) {
 // dual rows of the restoration rhs with the inertia-correction terms (delta_w, delta_c)
 __device__ __noinline__ void rhs_dual_resto(const Agent a, double mu, double dw, double dc) {
   const int lane = lane_now();
-  for (int c = lane; c < M; c += WAVE) {
-    const double lbv = a.lb()[c], ubv = a.ub()[c], slo = a.sL()[c], sup = a.sU()[c];
-    const double gvv = a.gv()[c], gsc = a.gs()[c], sv = a.s()[c], lm = a.lam()[c];
-    const double vl = a.vL()[c], vu = a.vU()[c];
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    const double lbv = a.lb()[c], slo = a.sL()[q], sup = a.sU()[q];
+    const double gvv = a.gv()[c], gsc = a.gs()[c], sv = a.s()[q], lm = a.lam()[c];
+    const double vl = a.vL()[q], vu = a.vU()[q];
     const double pv = a.rp()[c], nv = a.rn()[c], sgp = a.rzp()[c] / pv + dw, sgn = a.rzn()[c] / nv + dw;
-    const int cl = cls_of(lbv, ubv, slo, sup);
-    const double sg = sigma_s_v(sv, slo, sup, vl, vu);
+    const double sg = cl == 1 ? sigma_s_v(sv, slo, sup, vl, vu) : 0.0;  // used by inequality rows only
     double rr = -((cl == 0 ? gvv - gsc * lbv : gvv - sv) - pv + nv);
     if (cl == 1) {
       double gphis = 0.0;
@@ -3980,13 +4082,15 @@ __device__ __noinline__ double resto_resid(const Agent a, int first) {
     nrhs = fmax(nrhs, fabs(r0));
     nsol = fmax(nsol, fabs(gL.u.sol[b * NB + off]));
   }
-  for (int c = lane; c < M; c += WAVE) {
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
     const int b = c / NG, r = c % NG;
-    const double lbv = a.lb()[c], ubv = a.ub()[c], slo = a.sL()[c], sup = a.sU()[c];
-    const double gvv = a.gv()[c], gsc = a.gs()[c], sv = a.s()[c], lm = a.lam()[c];
+    const double lbv = a.lb()[c], slo = a.sL()[q], sup = a.sU()[q];
+    const double gvv = a.gv()[c], gsc = a.gs()[c], sv = a.s()[q], lm = a.lam()[c];
     const double pv = a.rp()[c], nv = a.rn()[c], sgp = a.rzp()[c] / pv + dw, sgn = a.rzn()[c] / nv + dw;
-    const int cl = cls_of(lbv, ubv, slo, sup);
-    const double sg = sigma_s_v(sv, slo, sup, a.vL()[c], a.vU()[c]);
+    const double sg = cl == 1 ? sigma_s_v(sv, slo, sup, a.vL()[q], a.vU()[q]) : 0.0;  // used by inequality rows only
     double rl = -((cl == 0 ? gvv - gsc * lbv : gvv - sv) - pv + nv);
     if (cl == 1) {
       double gphis = 0.0;
@@ -4057,14 +4161,16 @@ __device__ __noinline__ StepInfo recover_step_resto(const Agent a, double mu, do
     gphid += gphi * d;
   }
   for (int i = lane; i < NX; i += WAVE) a.dx()[i] = 0.0;
-  for (int c = lane; c < M; c += WAVE) {
-    const double lbv = a.lb()[c], ubv = a.ub()[c], slo = a.sL()[c], sup = a.sU()[c];
-    const double sv = a.s()[c], lm = a.lam()[c], vl = a.vL()[c], vu = a.vU()[c];
+  const unsigned cw = cls_word();
+  for (int sl = 0; sl < CS; ++sl) {
+    const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
+    if (c >= M) continue;
+    const double lbv = a.lb()[c], slo = a.sL()[q], sup = a.sU()[q];
+    const double sv = a.s()[q], lm = a.lam()[c], vl = a.vL()[q], vu = a.vU()[q];
     const double gvv = a.gv()[c], gsc = a.gs()[c];
     const double pv = a.rp()[c], nv = a.rn()[c], zp = a.rzp()[c], zn = a.rzn()[c];
     const double dlam = gL.u.sol[(c / NG) * NB + NP + c % NG];
     a.dl()[c] = dlam;
-    const int cl = cls_of(lbv, ubv, slo, sup);
     theta += fabs((cl == 0 ? gvv - gsc * lbv : gvv - sv) - pv + nv);
     double dsv = 0.0;
     if (cl == 1) {
@@ -4089,7 +4195,7 @@ __device__ __noinline__ StepInfo recover_step_resto(const Agent a, double mu, do
         bar += log(s_u);
       }
     }
-    a.ds()[c] = dsv;
+    if (cl != 0) a.ds()[q] = dsv;
     const double gp = RESTO_RHO - mu / pv, gn = RESTO_RHO - mu / nv;
     const double dp = (dlam - resto_r(-lm, mu / pv)) / (zp / pv + dw);
     const double dn = (-dlam - resto_r(lm, mu / nv)) / (zn / nv + dw);
@@ -4149,7 +4255,7 @@ __device__ __noinline__ void line_search_resto(const Agent a) {
         if (i < NW) {
           const double lo = a.xL()[i], hi = a.xU()[i];
           const double xt = a.x()[i] + alpha * a.dx()[i];
-          gL.u.t.xt[i] = xt;
+          trial().xt[i] = xt;
           if (i >= NX && lo != hi) {
             const double xrv = a.xr()[i];
             prox += dr2_of(xrv) * (xt - xrv) * (xt - xrv);
@@ -4170,15 +4276,15 @@ __device__ __noinline__ void line_search_resto(const Agent a) {
     const int lane = lane_now();
     const double alpha = K.ls.alpha;
     double th = 0.0, bar = 0.0, pn = 0.0;
+    const unsigned cw = cls_word();
 #pragma unroll 1
     for (int sl = 0; sl < CS; ++sl) {
-      const int c = lane + sl * WAVE;
+      const int c = lane + sl * WAVE, q = sidx_slot(cw, sl), cl = cls_slot(cw, sl);
       if (c < M) {
-        const double gsv = a.gs()[c], lbv = a.lb()[c], slv = a.sL()[c], suv = a.sU()[c];
-        const int cl = cls_of(lbv, a.ub()[c], slv, suv);
-        const double gt = gL.u.t.gt[c] * gsv;
-        gL.u.t.gt[c] = gt;
-        const double st = a.s()[c] + alpha * a.ds()[c];
+        const double gsv = a.gs()[c], lbv = a.lb()[c], slv = a.sL()[q], suv = a.sU()[q];
+        const double gt = trial().gt[c] * gsv;
+        trial().gt[c] = gt;
+        const double st = a.s()[q] + alpha * a.ds()[q];
         const double pt = a.rp()[c] + alpha * a.rdp()[c], nt = a.rn()[c] + alpha * a.rdn()[c];
         th += fabs((cl == 0 ? gt - gsv * lbv : gt - st) - pt + nt);
         if (cl == 1) {
@@ -4233,7 +4339,7 @@ __device__ __noinline__ void line_search_resto(const Agent a) {
 // take the restoration trial: accept_step plus p, n and their multipliers
 __device__ __noinline__ void accept_step_resto(const Agent a, const double kappa_sigma, double mu, double alpha,
                                                double az) {
-  accept_step(a, kappa_sigma, mu, alpha, az);
+  accept_step<false>(a, kappa_sigma, mu, alpha, az);
   const int lane = lane_now();
   for (int c = lane; c < M; c += WAVE) {
     const double pv = a.rp()[c], nv = a.rn()[c], dp = a.rdp()[c], dn = a.rdn()[c];
@@ -4502,11 +4608,17 @@ extern "C" __global__ void __launch_bounds__(64, MIN_WAVES) mpcx_ipm_solve(Args 
       const StepInfo st = recover_step_resto(a, K.mu, K.tau, K.dw);
       K.st = st;
     } else {
-#ifndef MPCX_NO_BARCACHE
-      const StepInfo st = recover_step(a, K.mu, K.tau, K.dw, K.obj_scale, K.bar_ok);
-#else  // diagnostics (A/B): the barrier recomputed at every iterate
-      const StepInfo st = recover_step(a, K.mu, K.tau, K.dw, K.obj_scale, 0);
+#ifdef MPCX_NO_BARCACHE  // diagnostics (A/B): the barrier recomputed at every iterate
+      const int bar_c = 0;
+#else
+      const int bar_c = K.bar_ok;
 #endif
+#ifdef MPCX_NO_THETACACHE  // diagnostics (A/B): the constraint violation summed again at every iterate
+      const int theta_c = 0;
+#else
+      const int theta_c = K.bar_ok;
+#endif
+      const StepInfo st = recover_step(a, K.mu, K.tau, K.dw, K.obj_scale, bar_c, theta_c);
       K.st = st;
     }
     PROF(7);
@@ -4530,7 +4642,7 @@ extern "C" __global__ void __launch_bounds__(64, MIN_WAVES) mpcx_ipm_solve(Args 
     K.fx = K.ls.tr.f;
     wsync();
     PROF(8);
-    accept_step(a, OPT(kappa_sigma), K.mu, K.ls.alpha, mode == 1 ? K.ls.alpha : K.st.az);
+    accept_step<STEP_RES>(a, OPT(kappa_sigma), K.mu, K.ls.alpha, mode == 1 ? K.ls.alpha : K.st.az);
     K.bar_val = K.ls.bar;        // the new iterate IS the last trial point: its barrier sum holds
     K.bar_ok = 1;
     sync();  // accepted multipliers visible to the stage lanes

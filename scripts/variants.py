@@ -116,6 +116,13 @@ VARIANTS = {
     # r06: the main build's stage elimination / assembly without the register image (MHE)
     "noreg": (["-DMPCX_ELIM_NOREG"], None),
     "asm_noreg": (["-DMPCX_ASM_NOREG"], None),
+    # r07: the slack-side arrays row-indexed again, the constraint violation summed again at every
+    # iterate, the Newton step through the workspace again (each part of the traffic cut switched off
+    # alone, then all three: the r06 data paths)
+    "rows_full": (["-DMPCX_ROWS_FULL"], None),
+    "no_thetacache": (["-DMPCX_NO_THETACACHE"], None),
+    "step_hbm": (["-DMPCX_STEP_HBM"], None),
+    "r06_paths": (["-DMPCX_ROWS_FULL", "-DMPCX_NO_THETACACHE", "-DMPCX_STEP_HBM"], None),
 }
 
 
@@ -199,7 +206,7 @@ def run(names):
             nat.solve(tp, tl, tu, tw, stats=st, stream=s.cuda_stream)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 5
+        reps = int(os.environ.get("REPS", "5"))  # launches in the timed window
         e0.record(s)
         for _ in range(reps):
             tw.copy_(tw0)
