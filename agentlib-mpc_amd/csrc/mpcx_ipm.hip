@@ -2404,6 +2404,7 @@ __device__ __forceinline__ Inertia factor(const Agent a, const KKTDiag kd) {
 #endif
 #else
   const unsigned long long dm = (N == 64) ? ~0ull : ((1ull << N) - 1ull);
+  if (lane_now() == 0) L.ks.n_dense += N;  // no static plan: every stage is factorised densely (and counted)
 #endif
   if (dm != 0ull) {
     const int nd = __popcll(dm);

@@ -128,7 +128,8 @@ typedef struct mpcx_stats {
   int32_t n_factorizations;
   int32_t n_trials;    /* line-search trial points evaluated */
   int32_t n_block_chain; /* factorisations that fell back to the sequential block chain */
-  int32_t n_dense_stages; /* stage factorisations redone densely (static sparse pivot rejected) */
+  int32_t n_dense_stages; /* stage factorisations done densely (static sparse pivot rejected; every stage of a
+                             build without the static plan, MPCX_NO_STATIC) */
   int32_t n_soft_restorations; /* line-search failures resolved by a soft restoration step */
   int32_t n_restoration_iters; /* iterations spent in the restoration phase (in iter_count) */
   int32_t n_filter_overflows;  /* filter insertions that dropped the oldest entry (cap 1024: 64 in

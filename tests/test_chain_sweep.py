@@ -3,7 +3,9 @@
 random symmetric indefinite blocks of the chain sizes (RNGRoom 4x4, MHE 6x6, NARX 7x7),
 including saddle blocks with a zero leading part (the bordered multipliers): the inverse
 and the inertia (which the inertia correction reads) must match.  The GPU parity cases of
-those models (tests/test_gpu_ipm.py, tests/test_gpu_admm.py) run the kernel itself."""
+those models (tests/test_gpu_ipm.py, tests/test_gpu_admm.py) run the kernel itself, and
+tests/test_ipm_linalg.py runs the device routine on its own, with this restatement's error
+against an mpmath reference as the unit of its tolerance."""
 
 import numpy as np
 import pytest
@@ -12,9 +14,14 @@ ALPHA = (1 + 17 ** 0.5) / 8   # BK_ALPHA
 ZERO_PIVOT = 1e-20
 
 
-def sweep(A0):
+#: the four Bunch-Kaufman branches a pivot step can take (``sweep(..., branches=[])`` records them)
+BRANCHES = ("k_first", "k_second", "r", "2x2")
+
+
+def sweep(A0, branches=None):
     """Line by line the kernel's loop: first unswept index k, BK pivot choice among the
-    unswept indices, one read-modify-write of the whole block per pivot."""
+    unswept indices, one read-modify-write of the whole block per pivot.  ``branches``: a list
+    that receives the branch of every pivot step (tests/ipm_linalg_harness.py)."""
     A = np.array(A0, float)
     n = len(A)
     done = np.zeros(n, bool)
@@ -27,14 +34,17 @@ def sweep(A0):
         lam = abs(A[r, k]) if cand else 0.0
         akk = abs(A[k, k])
         p, q = k, -1
+        branch = "k_first"
         if not (max(akk, lam) == 0.0 or akk >= ALPHA * lam):
             sigma = max(abs(A[r, j]) for j in range(n) if not done[j] and j != r)
             if akk * sigma >= ALPHA * lam * lam:
-                p = k
+                p, branch = k, "k_second"
             elif abs(A[r, r]) >= ALPHA * sigma:
-                p = r
+                p, branch = r, "r"
             else:
-                q = r
+                q, branch = r, "2x2"
+        if branches is not None:
+            branches.append(branch)
         B = A.copy()
         if q < 0:
             d = A[p, p]

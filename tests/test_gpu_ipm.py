@@ -150,6 +150,12 @@ def test_gpu_matches_oracle(name, kw, build):
     ref = _oracle(case, key=(name, repr(kw)))
     assert ref.success, ref.status
     res = _gpu_solve(case, n_copies=3, build=build)
+    assert_matches_oracle(case, name, kw, ref, res)
+
+
+def assert_matches_oracle(case, name, kw, ref, res):
+    """Every result of ``res`` against the oracle's ``ref``: objective to RTOL_OBJ, every variable
+    group on its grid to RTOL_TRAJ (also tests/test_gpu_ipm_fallbacks.py)."""
     nlp = case.backend.problem.nlp
     for r in res:
         assert r.stats["success"], r.stats
