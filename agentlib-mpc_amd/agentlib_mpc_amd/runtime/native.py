@@ -296,9 +296,21 @@ def default_options() -> Options:
 # ---------------------------------------------------------------------------
 # code objects
 # ---------------------------------------------------------------------------
+def kernel_sources(csrc: os.PathLike = CSRC) -> List[pathlib.Path]:
+    """Every file a model's code object is compiled from besides its generated source, in a fixed
+    order: the IPM kernel and its layers from ``csrc`` (another kernel tree put first on the include
+    path may hold them), the shared headers from this tree.  The one list: the code objects' cache
+    key, the test harnesses' keys and tests/test_native_abi.py (against the ``#include`` closure)."""
+    csrc = pathlib.Path(csrc)
+    # a tree without layers of its own gets this tree's through the later -I
+    ipm = csrc / "ipm" if (csrc / "ipm").is_dir() else CSRC / "ipm"
+    return [csrc / "mpcx_ipm.hip", *sorted(ipm.glob("*.h")),
+            CSRC / "mpcx_internal.h", CSRC / "mpcx_net_mfma.h", INCLUDE / "mpcx.h"]
+
+
 def _kernel_deps_hash() -> str:
     h = hashlib.sha1()
-    for p in (CSRC / "mpcx_ipm.hip", CSRC / "mpcx_internal.h", CSRC / "mpcx_net_mfma.h", INCLUDE / "mpcx.h"):
+    for p in kernel_sources():
         h.update(p.read_bytes())
     return h.hexdigest()[:10]
 

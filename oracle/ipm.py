@@ -29,7 +29,7 @@ import scipy.linalg
 
 INF = 1e19  # IPOPT nlp_lower/upper_bound_inf
 DEBUG = False
-ZERO_PIVOT = 1e-20  # same constant as csrc/mpcx_ipm.hip
+ZERO_PIVOT = 1e-20  # same constant as csrc/ipm/bk.h
 
 
 #: diagnostics only: a list receives the trials of the last line search (scripts/resto_diag.py)

@@ -29,16 +29,22 @@ def one(src, inc):
     return src.name, f"LDS {get('LDS Size')} B, occupancy {get('Occupancy')} waves/SIMD, VGPRs {get('VGPRs')}, scratch {get('ScratchSize')}"
 
 
-def main():
-    inc = sys.argv[1] if len(sys.argv) > 1 else str(native.CSRC)
-    # the main builds' generated sources (variants differ by -D flags only); any kernel hash: the
-    # generated part does not depend on it, the kernel source comes from `inc`
+def main_sources():
+    """The main builds' generated sources in the kernel cache, one per structure (variants differ by
+    -D flags only); any kernel hash: the generated part does not depend on it, the kernel source
+    comes from the include path."""
     seen, srcs = set(), []
     for p in sorted(native.KERNEL_DIR.glob("mpcx_*_gfx950.hip")):
         parts = p.name.split("_")
         if len(parts) == 4 and parts[1] not in seen:  # mpcx_<key>_<hash>_gfx950.hip
             seen.add(parts[1])
             srcs.append(p)
+    return srcs
+
+
+def main():
+    inc = sys.argv[1] if len(sys.argv) > 1 else str(native.CSRC)
+    srcs = main_sources()
     with cf.ThreadPoolExecutor(6) as ex:
         for name, info in ex.map(lambda s: one(s, inc), srcs):
             print(f"{name:60s} {info}", flush=True)

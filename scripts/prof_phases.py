@@ -3,6 +3,7 @@ import os, sys, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "agentlib-mpc_amd")]
 import numpy as np
+from kernel_tree import materialise
 
 CHAIN_PATCH = [
     ("SPROF(6);  // loads and the per-element terms", "(void)0;"),
@@ -23,20 +24,13 @@ def build_profile_hsaco(gen, wslds=False):
     src = native.KERNEL_DIR / f"prof_{gen.key}{'_wslds' if wslds else ''}.hip"
     out = src.with_suffix(".hsaco")
     src.parent.mkdir(parents=True, exist_ok=True)
-    text = gen.source
+    tree = []
     if os.environ.get("CHAIN_PROF", "0") == "1":
         # the twisted chain's three phases in the iteration head's profile slots (6-8), on a
-        # patched copy of the kernel source (the shipped source stays as it is)
-        k = (native.CSRC / "mpcx_ipm.hip").read_text()
-        for a, b in CHAIN_PATCH:
-            assert k.count(a) == 1, a
-            k = k.replace(a, b)
-        kp = src.with_name(src.stem + "_chainprof_ipm.hip")
-        kp.write_text(k)
-        text = text.replace('#include "mpcx_ipm.hip"', f'#include "{kp}"')
-        assert str(kp) in text
-    src.write_text("#define MPCX_PROFILE 1\n" + ("#define MPCX_WS_LDS 1\n" if wslds else "") + text)
-    subprocess.run([native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17",
+        # patched copy of the kernel sources (the shipped sources stay as they are)
+        tree = [f"-I{materialise(src.with_name(src.stem + '_chainprof_tree'), replace=CHAIN_PATCH, unique=True)}"]
+    src.write_text("#define MPCX_PROFILE 1\n" + ("#define MPCX_WS_LDS 1\n" if wslds else "") + gen.source)
+    subprocess.run([native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", *tree,
                     f"-I{native.INCLUDE}", f"-I{native.CSRC}", str(src), "-o", str(out)], check=True)
     return out
 

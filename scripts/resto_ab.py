@@ -19,6 +19,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "agentlib-mpc_amd")]
 
+from kernel_tree import materialise  # noqa: E402
+
 KW = {"T_lb": 255.0, "T_ub": 302.0, "disturbance": 270.0, "T0": 290.0}
 REF = dict(tol=1e-4, max_iter=100, acceptable_tol=0.1, acceptable_iter=5,
            acceptable_constr_viol_tol=1.0, acceptable_compl_inf_tol=1.0)
@@ -48,19 +50,12 @@ def build(names):
     d.mkdir(parents=True, exist_ok=True)
     for name in names:
         defs, rev = VARIANTS[name]
-        src_text = gen.source
-        if rev is not None:
-            ktxt = subprocess.run(["git", "-C", ROOT, "show", f"{rev}:agentlib-mpc_amd/csrc/mpcx_ipm.hip"],
-                                  capture_output=True, text=True, check=True).stdout
-            kp = d / f"mpcx_ipm_{name}.hip"
-            kp.write_text(ktxt)
-            src_text = src_text.replace('#include "mpcx_ipm.hip"', f'#include "{kp}"')
-            assert str(kp) in src_text
+        tree = [f"-I{materialise(d / f'tree_{name}', rev=rev)}"] if rev is not None else []
         src = d / f"{BUILD}_{name}.hip"
-        src.write_text(src_text)
+        src.write_text(gen.source)
         out = d / f"{BUILD}_{name}.hsaco"
         extra = ["-DMPCX_WS_LDS"] if BUILD == "lds" else []
-        subprocess.run([native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", *extra, *defs,
+        subprocess.run([native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", *extra, *defs, *tree,
                         f"-I{native.INCLUDE}", f"-I{native.CSRC}", str(src), "-o", str(out)], check=True)
         print("built", out, flush=True)
 

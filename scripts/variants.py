@@ -3,7 +3,8 @@
 ``python scripts/variants.py build`` (CPU) compiles every variant below into
 ``_build/variants/``; ``python scripts/variants.py run`` (GPU) times them on the
 bench fleet and checks each against the default build's solution.
-A variant = extra -D defines and/or a source transform of mpcx_ipm.hip.
+A variant = extra -D defines and/or another kernel tree (scripts/kernel_tree.py): a revision's, or the
+working tree's with a text replacement.
 """
 import json
 import os
@@ -14,6 +15,8 @@ import time
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT), str(ROOT / "agentlib-mpc_amd")]
+
+from kernel_tree import materialise  # noqa: E402
 
 VARIANTS = {
     "base": ([], None),
@@ -32,7 +35,7 @@ VARIANTS = {
     # 5 / 6 agents per CU with <= 256 registers: some SIMDs hold two waves
     "apc5_w2": (["-DMPCX_LDS_TARGET_OVERRIDE=32512", "-DMPCX_MIN_WAVES=2"], None),
     "apc6_w2": (["-DMPCX_LDS_TARGET_OVERRIDE=27050", "-DMPCX_MIN_WAVES=2"], None),
-    "apc5": (["-DMPCX_LDS_TARGET_OVERRIDE=32512"], None),
+    "lds32k": (["-DMPCX_LDS_TARGET_OVERRIDE=32512"], None),
     "apc8": (["-DMPCX_LDS_TARGET_OVERRIDE=20224"], None),
     "w1": (["-DMPCX_MIN_WAVES=1"], None),
     "inl_w2": (["-DMPCX_MIN_WAVES=2"], ("__noinline__", "__attribute__((always_inline))")),
@@ -64,17 +67,12 @@ VARIANTS = {
     "elimreg": (["-DMPCX_ELIM_FORCE_REG"], None),
     "elimreg_w1": (["-DMPCX_ELIM_FORCE_REG", "-DMPCX_MIN_WAVES=1"], None),
     "lds_noreg": (["-DMPCX_WS_LDS", "-DMPCX_ELIM_NOREG"], None),
-    # r04: the register image loaded from the LDS image the GC lanes assembled (no assemble_reg)
-    "asm_noreg": (["-DMPCX_ASM_NOREG"], None),
-    "noreg": (["-DMPCX_ELIM_NOREG"], None),
     # r04: the one-sided state chain instead of the twisted one
     "chain_seq": (["-DMPCX_CHAIN_SEQ"], None),
     "lds_nofence": (["-DMPCX_WS_LDS", "-DMPCX_ELIM_FENCE=(void)0"], None),
     # r04: more than 16 agents per CU for structures with a small LDS share and register need
     "apc12": (["-DMPCX_APC=12"], None),
     "apc16": (["-DMPCX_APC=16"], None),
-    "apc20": (["-DMPCX_APC=20"], None),
-    "apc24": (["-DMPCX_APC=24"], None),
     "apc32": (["-DMPCX_APC=32"], None),
     "lds_asm_noreg": (["-DMPCX_WS_LDS", "-DMPCX_ASM_NOREG"], None),
     # r05: the kernel source of any revision (REV=<sha>) against the working tree, fleet and
@@ -113,7 +111,8 @@ VARIANTS = {
     "apc20": (["-DMPCX_APC=20"], None),
     "apc24": (["-DMPCX_APC=24"], None),
     "apc28": (["-DMPCX_APC=28"], None),
-    # r06: the main build's stage elimination / assembly without the register image (MHE)
+    # r06: the main build's stage elimination / assembly without the register image (MHE; asm_noreg, r04:
+    # the register image loaded from the LDS image the GC lanes assembled, no assemble_reg)
     "noreg": (["-DMPCX_ELIM_NOREG"], None),
     "asm_noreg": (["-DMPCX_ASM_NOREG"], None),
     # r07: the slack-side arrays row-indexed again, the constraint violation summed again at every
@@ -140,26 +139,15 @@ def build(names):
     d.mkdir(parents=True, exist_ok=True)
     for name in names:
         defs, tr = VARIANTS[name]
-        kern = native.CSRC / "mpcx_ipm.hip"
-        src_text = gen.source
-        if tr is not None:
-            if isinstance(tr, str):
-                rev = "HEAD" if tr == "HEAD" else tr.split(":", 1)[1]
-                ktxt = subprocess.run(["git", "-C", str(ROOT), "show", f"{rev}:agentlib-mpc_amd/csrc/mpcx_ipm.hip"],
-                                      capture_output=True, text=True, check=True).stdout
-            else:
-                ktxt = kern.read_text()
-                for pair in (tr if isinstance(tr, list) else [tr]):
-                    assert pair[0] in ktxt, f"{name}: pattern not found"
-                    ktxt = ktxt.replace(*pair)
-            kp = d / f"mpcx_ipm_{name}.hip"
-            kp.write_text(ktxt)
-            src_text = src_text.replace('#include "mpcx_ipm.hip"', f'#include "{kp}"')
-            assert str(kp) in src_text, "kernel include not found in generated source"
+        tree = []
+        if isinstance(tr, str):    # "HEAD" or "REV:<sha>"
+            tree = [f"-I{materialise(d / f'tree_{name}', rev=tr.split(':', 1)[-1])}"]
+        elif tr is not None:       # an (old, new) pair or a list of them
+            tree = [f"-I{materialise(d / f'tree_{name}', replace=tr if isinstance(tr, list) else [tr])}"]
         src = d / f"{name}.hip"
-        src.write_text(src_text)
+        src.write_text(gen.source)
         out = d / f"{name}.hsaco"
-        cmd = [native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", *defs,
+        cmd = [native._hipcc(), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", *defs, *tree,
                f"-I{native.INCLUDE}", f"-I{native.CSRC}", str(src), "-o", str(out),
                "-Rpass-analysis=kernel-resource-usage"]
         r = subprocess.run(cmd, capture_output=True, text=True, check=True)

@@ -1,11 +1,14 @@
-"""Device unit harness of the IPM kernel's dense Bunch-Kaufman routines (csrc/mpcx_ipm.hip:
-``bk_sweep``, ``bk_sweep2``, ``bk_factor`` + ``bk_inverse``, ``interior_bk`` +
+"""Device unit harness of the IPM kernel's dense Bunch-Kaufman routines (csrc/ipm/bk.h:
+``bk_sweep``, ``bk_sweep2``, ``bk_factor`` + ``bk_inverse``; csrc/mpcx_ipm.hip: ``interior_bk`` +
 ``trailing_backsolve``), support code of tests/test_ipm_linalg.py.
 
-The source is a generated model source (it ends with ``#include "mpcx_ipm.hip"``) with wrapper
-kernels appended inside ``namespace mpcx_kernel``; it is compiled device-only (``--genco``, as the
-model's own code object) and launched through a small host launcher (hipModuleLoad /
-hipModuleLaunchKernel) loaded with ctypes.  A wrapper runs one wavefront per workgroup on one
+The routines of bk.h at the model-free sizes are built from a source that includes only the kernel's
+two model-free layers (ipm/wave.h, ipm/bk.h; no ``MPCX_*`` dimension is defined); what depends on a
+structure (the interior pair, the block chain's ``NB x LDB`` factor) from that structure's generated
+model source (it ends with ``#include "mpcx_ipm.hip"``).  Either way wrapper kernels are appended
+inside ``namespace mpcx_kernel``; the source is compiled device-only (``--genco``, as a model's own
+code object) and launched through a small host launcher (hipModuleLoad / hipModuleLaunchKernel)
+loaded with ctypes.  A wrapper runs one wavefront per workgroup on one
 matrix (the interior wrapper: on the ``64 / G`` packed stage images of one wave).  It stages the
 LDS arrays from global memory, puts a sentinel into 8 guard entries behind every LDS array, fills
 the outputs with NaN (integers: a poison value), calls the routine and copies every array back
@@ -43,7 +46,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import mpmath as mp
 import numpy as np
 
-from agentlib_mpc_amd.runtime import native
+from agentlib_mpc_amd.runtime import codegen, native
 from tests import configs
 from tests.eval_harness_core import (DPS, FACTOR, FLOOR, GUARD, ROOT, SENTINEL, _cache_dir,
                                      name_seed, upload)
@@ -548,30 +551,35 @@ def bound(recorded: float) -> float:
 
 @dataclasses.dataclass(frozen=True)
 class Config:
-    """The harness of one structure: the size-generic kernels (sweeps, LDL^T + inverse at the
-    listed sizes) live in the ``one_room`` harness, the block-chain size in its structure's."""
-    case: str
+    """One harness source: a structure's (``case``: the interior pair, the block-chain size), or the
+    model-free one (``case`` None: sweeps, LDL^T + inverse at the listed sizes)."""
+    case: Optional[str]
     sweeps: Tuple[Tuple[int, int], ...] = ()
     factors: Tuple[Tuple[int, int], ...] = ()
     interior: bool = False
 
     @property
     def name(self) -> str:
-        return self.case
+        return self.case or "dense"
 
 
-def _configs() -> Tuple[Config, ...]:
-    sw = tuple((n, ld) for n in SWEEP_SIZES for ld in (n, n + 1))
-    fa = tuple((n, n) for n in FACTOR_SIZES)
-    out = []
-    for case in INTERIOR_CASES:
-        out.append(Config(case, sw if case == "one_room" else (), fa if case == "one_room" else (), True))
-    out.append(Config(LARGEST_BLOCK_CASE, (), (("NB", "LDB"),), False))
-    return tuple(out)
+#: the model-free source: every size of the sweeps and of the LDL^T + inverse pair
+DENSE = Config(None, tuple((n, ld) for n in SWEEP_SIZES for ld in (n, n + 1)), tuple((n, n) for n in FACTOR_SIZES))
+CONFIGS = (*(Config(case, interior=True) for case in INTERIOR_CASES),
+           Config(LARGEST_BLOCK_CASE, factors=(("NB", "LDB"),)))
+BY_NAME = {c.name: c for c in (DENSE, *CONFIGS)}
 
+#: what the model-free source includes, all of it
+DENSE_INCLUDES = ("hip/hip_runtime.h", "ipm/wave.h", "ipm/bk.h")
 
-CONFIGS = _configs()
-BY_NAME = {c.name: c for c in CONFIGS}
+# a structure's source only: the kernel's constants
+_CONSTS = f"""
+extern "C" __global__ void __launch_bounds__(64) ipmla_consts(int* __restrict__ out, int n) {{
+  const int v[{len(CONST_NAMES)}] = {{{", ".join(CONST_NAMES)}}};
+  if (threadIdx.x == 0 && blockIdx.x == 0)
+    for (int i = 0; i < {len(CONST_NAMES)} && i < n; ++i) out[i] = v[i];
+}}
+"""
 
 _COMMON = f"""
 // generated by tests/ipm_linalg_harness.py: wrapper kernels of the dense Bunch-Kaufman routines
@@ -580,12 +588,6 @@ namespace mpcx_kernel {{
 #define H_SENT ({SENTINEL!r})
 #define H_ISENT ({ISENTINEL})
 #define H_IPOISON ({IPOISON})
-
-extern "C" __global__ void __launch_bounds__(64) ipmla_consts(int* __restrict__ out, int n) {{
-  const int v[{len(CONST_NAMES)}] = {{{", ".join(CONST_NAMES)}}};
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    for (int i = 0; i < {len(CONST_NAMES)} && i < n; ++i) out[i] = v[i];
-}}
 
 __device__ __forceinline__ void h_put(int* res, const Inertia in, int bad) {{
   res[0] = in.pos; res[1] = in.neg; res[2] = in.zero; res[3] = bad;
@@ -694,8 +696,15 @@ def kernel_name(kind: str, n, ld) -> str:
     return f"ipmla_{kind}_{n}_{ld}"
 
 
+def dense_head() -> str:
+    """What the wrappers of bk.h need in front of them: the two model-free layers and the reciprocal
+    ``MPCX_RCP`` as the code generator writes it into every model source."""
+    first, *layers = DENSE_INCLUDES
+    return f"#include <{first}>\n" + "\n".join(codegen.RCP_LINES) + "\n" + "".join(f'#include "{name}"\n' for name in layers)
+
+
 def source(c: Config) -> str:
-    parts = [case_gen(c.case).source, _COMMON]
+    parts = [dense_head(), _COMMON] if c.case is None else [case_gen(c.case).source, _COMMON, _CONSTS]
     for n, ld in c.sweeps:
         parts.append(f"""
 extern "C" __global__ void __launch_bounds__(64) {kernel_name("sweep", n, ld)}(
@@ -761,14 +770,12 @@ def _compile(text: str, stem: str, suffix: str, flags: Sequence[str], deps: Sequ
 
 def build(c: Config, include_dir: Optional[os.PathLike] = None) -> pathlib.Path:
     """The code object of config ``c`` (device-only, the flags of ``native.compile_model``; cached by
-    the hash of the source, the headers and the command).  ``include_dir``: where mpcx_ipm.hip is
-    taken from (a mutated copy)."""
+    the hash of the source, ``native.kernel_sources`` and the command).  ``include_dir``: where the
+    kernel (mpcx_ipm.hip, ipm/) is taken from (a mutated copy)."""
     csrc = pathlib.Path(include_dir) if include_dir is not None else native.CSRC
     flags = ["--genco", f"--offload-arch={native.OFFLOAD_ARCH}", "-O3", "-std=c++17", f"-I{native.INCLUDE}",
              f"-I{csrc}", f"-I{native.CSRC}"]
-    deps = [(csrc / "mpcx_ipm.hip").read_bytes()]
-    deps += [p.read_bytes() for p in (native.CSRC / "mpcx_internal.h", native.CSRC / "mpcx_net_mfma.h",
-                                      native.INCLUDE / "mpcx.h")]
+    deps = [p.read_bytes() for p in native.kernel_sources(csrc)]
     return _compile(source(c), f"ipm_linalg_{c.name}", ".hsaco", flags, deps)
 
 

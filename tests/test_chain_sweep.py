@@ -1,5 +1,5 @@
 """The state-chain pivot blocks are inverted by a Bunch-Kaufman-pivoted symmetric sweep
-(csrc/mpcx_ipm.hip ``bk_sweep``); this is its host restatement, checked against numpy on
+(csrc/ipm/bk.h ``bk_sweep``); this is its host restatement, checked against numpy on
 random symmetric indefinite blocks of the chain sizes (RNGRoom 4x4, MHE 6x6, NARX 7x7),
 including saddle blocks with a zero leading part (the bordered multipliers): the inverse
 and the inertia (which the inertia correction reads) must match.  The GPU parity cases of

@@ -1,4 +1,4 @@
-"""The dense Bunch-Kaufman routines of csrc/mpcx_ipm.hip on the device, one routine at a time:
+"""The dense Bunch-Kaufman routines of the IPM kernel (csrc/ipm/bk.h, csrc/mpcx_ipm.hip) on the device, one routine at a time:
 ``bk_sweep``, ``bk_sweep2``, ``bk_factor`` + ``bk_inverse`` and ``interior_bk`` +
 ``trailing_backsolve`` against an mpmath reference (tests/ipm_linalg_harness.py: wrappers,
 matrices, references, what is pinned at a zero pivot and why).
@@ -143,12 +143,27 @@ def test_structures_of_the_harness():
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-@pytest.mark.parametrize("name", [c.name for c in h.CONFIGS])
+@pytest.mark.parametrize("name", list(h.BY_NAME))
 def test_harness_source_compiles_for_gfx950(name):
-    """Device-only, with the static_assert of what the structure is in the harness for."""
+    """Device-only, with the static_assert of what the structure is in the harness for.  The
+    model-free source: csrc/ipm/wave.h and csrc/ipm/bk.h compile, and the four routines of bk.h
+    instantiate, in a translation unit that includes nothing else of the kernel and defines no
+    ``MPCX_*`` dimension (the reciprocal ``MPCX_RCP`` is the code generator's)."""
+    import re
+
     c = h.BY_NAME[name]
     src = h.source(c)
-    assert src.count('#include "mpcx_ipm.hip"') == 1 and src.index("ipmla_consts") > src.index('#include "mpcx_ipm.hip"')
+    wrappers = src.index("// generated by tests/ipm_linalg_harness.py")
+    if c.case is None:
+        assert tuple(re.findall(r'#include [<"]([^>"]+)[>"]', src)) == h.DENSE_INCLUDES
+        assert wrappers > src.index('#include "ipm/bk.h"') > src.index('#include "ipm/wave.h"')
+        assert set(re.findall(r"#define (MPCX_\w+)", src)) == {"MPCX_RCP"} and "ipmla_consts" not in src
+        assert all(f"{r}<" in src for r in ("bk_sweep", "bk_sweep2", "bk_factor", "bk_inverse"))
+        assert {(n, ld) for n in h.SWEEP_SIZES for ld in (n, n + 1)} == set(c.sweeps)
+        assert {(n, n) for n in h.FACTOR_SIZES} == set(c.factors)
+    else:
+        assert src.count('#include "mpcx_ipm.hip"') == 1 and wrappers > src.index('#include "mpcx_ipm.hip"')
+        assert src.index("ipmla_consts") > wrappers and not c.sweeps
     assert ("ipmla_interior" in src) == c.interior
     path = h.build(c)
     assert path.exists() and path.stat().st_size > 0
@@ -210,7 +225,7 @@ def report(what, n, worst):
 @pytest.mark.parametrize("n,ld", SWEEP_CASES)
 def test_bk_sweep(n, ld, modules):
     mats = h.matrices(n)
-    ab, ob, res = h.run_sweep(modules("one_room"), n, ld, [m.A for m in mats])
+    ab, ob, res = h.run_sweep(modules(h.DENSE.name), n, ld, [m.A for m in mats])
     _, apad, aguard = _images(ab, n, ld)
     out, opad, oguard = _images(ob, n, ld)
     assert np.array_equal(aguard, np.tile(SENT, (len(mats), 1))) and np.array_equal(oguard, aguard)
@@ -232,7 +247,7 @@ def test_bk_sweep2(n, ld, modules):
     mats, pairs = h.matrices(n), h.sweep2_pairs(n)
     A = [mats[a].A for a, _, _ in pairs]
     B = [mats[b].A for _, b, _ in pairs]
-    ab, bb, res = h.run_sweep2(modules("one_room"), n, ld, A, B, [int(t) for _, _, t in pairs])
+    ab, bb, res = h.run_sweep2(modules(h.DENSE.name), n, ld, A, B, [int(t) for _, _, t in pairs])
     ga, apad, aguard = _images(ab, n, ld)
     gb, bpad, bguard = _images(bb, n, ld)
     assert np.array_equal(aguard, np.tile(SENT, (len(pairs), 1))) and np.array_equal(bguard, aguard)
@@ -280,7 +295,7 @@ def check_factor(n, ld, db, ib, res):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", h.FACTOR_SIZES)
 def test_bk_factor_inverse(n, modules):
-    db, ib, res = h.run_factor(modules("one_room"), n, n, [m.A for m in h.matrices(n)])
+    db, ib, res = h.run_factor(modules(h.DENSE.name), n, n, [m.A for m in h.matrices(n)])
     check_factor(n, n, db, ib, res)
 
 

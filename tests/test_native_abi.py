@@ -306,17 +306,38 @@ def test_compile_model_command_line(tmp_path, monkeypatch, variant, defines):
     assert not out.with_suffix(".nofit").exists()   # a transient failure leaves no marker
 
 
-def test_code_object_key_is_made_of_the_same_four_files():
-    """The code objects' names carry the hash of the kernel source and the three headers it
-    includes -- not of csrc/mpcx_builds.h, which is host code."""
+def test_code_object_key_is_made_of_the_include_closure():
+    """The code objects' names carry the hash of ``native.kernel_sources()`` in list order, and that
+    list is exactly what a generated source pulls in: the quoted ``#include``s of the code generator
+    (mpcx_ipm.hip, mpcx_net_mfma.h) followed transitively, resolved against the including file's
+    directory, csrc/ and include/.  A header somebody adds to the kernel and forgets in the list
+    fails here instead of serving stale code objects.  csrc/mpcx_builds.h is host code: in none."""
     import hashlib
+    import inspect
+    import re
 
+    from agentlib_mpc_amd.runtime import codegen
+
+    quoted = re.compile(r'#include "([^"]+)"')
+    todo = [native.CSRC / n for n in sorted(set(quoted.findall(inspect.getsource(codegen))))]
+    assert native.CSRC / "mpcx_ipm.hip" in todo
+    closure = set()
+    while todo:
+        p = todo.pop()
+        if p in closure:
+            continue
+        closure.add(p)
+        for name in quoted.findall(p.read_text()):
+            found = [d / name for d in (p.parent, native.CSRC, native.INCLUDE) if (d / name).is_file()]
+            assert found, (p, name)
+            todo.append(found[0])
+    sources = native.kernel_sources()
+    assert len(sources) == len(set(sources)) and sources[0] == native.CSRC / "mpcx_ipm.hip"
+    assert closure == set(sources), sorted(str(p) for p in closure ^ set(sources))
     h = hashlib.sha1()
-    for p in (native.CSRC / "mpcx_ipm.hip", native.CSRC / "mpcx_internal.h", native.CSRC / "mpcx_net_mfma.h",
-              native.INCLUDE / "mpcx.h"):
+    for p in sources:
         h.update(p.read_bytes())
     assert native._kernel_deps_hash() == h.hexdigest()[:10]
-    for p in (native.CSRC / "mpcx_ipm.hip", native.CSRC / "mpcx_internal.h", native.CSRC / "mpcx_net_mfma.h",
-              native.INCLUDE / "mpcx.h"):
+    for p in sources:
         assert "mpcx_builds.h" not in p.read_text()
     assert '#include "mpcx_builds.h"' in (native.CSRC / "mpcx_runtime.cpp").read_text()
