@@ -59,7 +59,8 @@ def full_matrix(S11, S00, S10, fix, NX, NMU):
     return T
 
 
-def one_sided(S11, S00, S10, fix, NX, NMU, rhs):
+def one_sided(S11, S00, S10, fix, NX, NMU, rhs, out=None):
+    """``out``: a dict that receives the pivot inverses (``Dinv``)."""
     N = len(S11)
     Dinv, inert = [], np.zeros(3, int)
     for j in range(N):
@@ -78,12 +79,15 @@ def one_sided(S11, S00, S10, fix, NX, NMU, rhs):
         if j + 1 < N:
             t[NMU:] -= S10[j + 1].T @ c[j + 1]
         c[j] = Dinv[j] @ t
+    if out is not None:
+        out["Dinv"] = Dinv
     return np.concatenate(c), tuple(inert)
 
 
-def twisted(S11, S00, S10, fix, NX, NMU, rhs):
+def twisted(S11, S00, S10, fix, NX, NMU, rhs, out=None):
     """Line by line chain_factor_tw / chain_solve_tw (their step order: forward pivot jf = s and
-    backward pivot jb = N-1-s together, the middle pivot CMID = N // 2 at step CSTEPS)."""
+    backward pivot jb = N-1-s together, the middle pivot CMID = N // 2 at step CSTEPS).  ``out``: a
+    dict that receives the pivot inverses (``Dinv``)."""
     N = len(S11)
     CMID = N // 2
     CSTEPS = max(CMID, N - 1 - CMID)
@@ -150,6 +154,8 @@ def twisted(S11, S00, S10, fix, NX, NMU, rhs):
             new[jb] = Dinv[jb] @ (xs[jb] - S10[jb] @ xs[jb - 1][NMU:])
         for j, v in new.items():
             xs[j] = v
+    if out is not None:
+        out["Dinv"] = Dinv
     return np.concatenate(xs), tuple(inert)
 
 

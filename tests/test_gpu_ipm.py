@@ -377,7 +377,7 @@ def test_gpu_infeasible_run_ends_without_nonfinite_iterates(build):
 def test_gpu_filter_matches_oracle(mode, build, monkeypatch):
     """The filter (IPOPT Filter::AddEntry: dominated entries removed on insertion; IPOPT's list is
     unbounded) against the oracle's on the cubic_room restoration case, which holds up to 22
-    entries: the shipped build (64 in LDS + 960 in the spill list) never spills; a test build with
+    entries: the shipped build (48 in LDS + 976 in the spill list) never spills; a test build with
     8 entries in LDS moves the older ones to the spill list and must follow the oracle's unbounded
     (1024) filter exactly -- same path, no overflow; a test build holding 12 in all (8 + 4)
     overflows, dropping the oldest entry, exactly as the oracle with max_filter = 12 does."""

@@ -15,12 +15,15 @@ import torch
 
 from agentlib_mpc_amd.runtime import native
 from tests import configs
+from tests.ipm_linalg_harness import nmu_of
 from tests.test_gpu_ipm import RTOL_OBJ, _gpu_solve, _oracle, assert_matches_oracle
 
 pytestmark = pytest.mark.gpu
 
 CASES = ["one_room", "rng_room_mpc", "mhe_room"]
-CHAIN_CASES = ["rng_room_mpc", "mhe_room"]     # NX > 1: the chain pivots are blocks
+#: the chain flags on structures whose chain they change: blocks (NX > 1) for the LDL^T pair, the
+#: scalar chain (NX = 1, no bordered rows, one DPP row: the scan is the shipped path) for the recurrence
+CHAIN_VARIANTS = {"MPCX_CHAIN_BK": ["rng_room_mpc", "mhe_room"], "MPCX_CHAIN_SERIAL": ["one_room", "cubic_room"]}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -55,12 +58,16 @@ def test_forced_fallback_matches_oracle(define, counter, name, monkeypatch):
     print(define, name, [(r.stats["iter_count"], r.stats[counter]) for r in res])
 
 
-@pytest.mark.parametrize("name", CHAIN_CASES)
-@pytest.mark.parametrize("define", ["MPCX_CHAIN_BK", "MPCX_CHAIN_SERIAL"])
+@pytest.mark.parametrize("define,name", [(d, n) for d, names in CHAIN_VARIANTS.items() for n in names])
 def test_chain_variant_matches_the_shipped_chain(define, name, monkeypatch):
-    """The chain pivots through ``bk_factor`` + ``bk_inverse`` instead of the sweep, and the serial
-    recurrence instead of the scan: the same path as the unflagged build."""
-    assert configs.CASES[name]().backend.problem.gen.dims["NX"] > 1
+    """The chain pivots through ``bk_factor`` + ``bk_inverse`` instead of the sweep (block chains),
+    and the serial recurrence instead of the scan (scalar chains, where alone the flag acts): the
+    same path as the unflagged build."""
+    d = configs.CASES[name]().backend.problem.gen
+    if define == "MPCX_CHAIN_SERIAL":   # acts inside ``if constexpr (NX == 1 && NMU == 0)`` only
+        assert d.dims["NX"] == 1 and nmu_of(d) == 0 and d.dims["N"] <= 16
+    else:
+        assert d.dims["NX"] > 1
     _, base = _solve_main(name, monkeypatch)
     _, res = _solve_main(name, monkeypatch, define)
     for r, b in zip(res, base):
