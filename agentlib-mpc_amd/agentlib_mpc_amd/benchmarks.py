@@ -492,6 +492,7 @@ def compile_all(verbose: bool = False):
     # rows on both sides of the 64-row slots of the packed slack arrays (tests/test_gpu_row_compaction.py)
     for n_ in (9, 10, 19):
         variants[f"one_room_n{n_}"] = lambda n_=n_: one_room(N=n_)
+    variants["one_room_n2"] = lambda: one_room(N=2)  # one stage boundary (tests/test_gpu_accepted_handoff.py)
     from concurrent.futures import ThreadPoolExecutor
 
     probs = {name: fn()[0].problem for name, fn in variants.items()}
@@ -521,12 +522,40 @@ def compile_all(verbose: bool = False):
                 path = native.compile_model(gen, False, v)
                 if verbose:
                     print(f"[mpcx] cubic_room {defines}{label[v]}: {path.name if path else '-'}")
+        # main builds with the accepted-point hand-off switched back, part by part and as a whole
+        # (tests/test_gpu_accepted_handoff.py compares them with the shipped builds)
+        todo = [(name, defines, None) for name, defs in HANDOFF_TEST_BUILDS.items() for defines in defs]
+        todo += [(name, defines, native.SMALL_FLEET) for name, defs in HANDOFF_TEST_BUILDS_LDS.items() for defines in defs]
+        with ThreadPoolExecutor(max_workers=jobs) as ex:
+            built = ex.map(lambda t: native.compile_model(probs[t[0]].gen, False, t[2], defines=t[1]), todo)
+            for (name, defines, v), path in zip(todo, built):
+                if verbose:
+                    print(f"[mpcx] {name} {defines}{label[v]}: {path.name if path else '-'}")
     finally:
         if saved is None:
             os.environ.pop("MPCX_DEFINES", None)
         else:
             os.environ["MPCX_DEFINES"] = saved
     return paths
+
+
+#: the switches that restore the previous hand-off from the acceptance to the derivative passes and
+#: the factorisation (csrc/mpcx_ipm.hip), in the order of the parts A-D
+HANDOFF_SWITCHES = ("MPCX_GS_HBM", "MPCX_LAM_HBM", "MPCX_HESS_PHASE", "MPCX_LP_ALL")
+HANDOFF_ALL_OFF = ",".join(HANDOFF_SWITCHES)
+#: structure (a name of compile_all's list) -> MPCX_DEFINES values of its test builds
+HANDOFF_TEST_BUILDS = {
+    "one_room": [HANDOFF_ALL_OFF, *HANDOFF_SWITCHES, "MPCX_NO_STATIC", "MPCX_NO_STATIC," + HANDOFF_ALL_OFF],
+    "one_room_n2": [HANDOFF_ALL_OFF],
+    "one_room_n10": [HANDOFF_ALL_OFF],
+    "one_room_n19": [HANDOFF_ALL_OFF, "MPCX_GS_HBM"],
+    "mhe_room": [HANDOFF_ALL_OFF],
+    "room_nn_n8": [HANDOFF_ALL_OFF],
+    "fixture_mpc": [HANDOFF_ALL_OFF],
+    "one_room_switch": [HANDOFF_ALL_OFF],
+}
+#: the same for the small-fleet build (workspace in LDS), where parts B and D act
+HANDOFF_TEST_BUILDS_LDS = {"one_room": [HANDOFF_ALL_OFF]}
 
 
 #: the filter's capacity (csrc/mpcx_ipm.hip MAXF + FSPILL; oracle/ipm.py max_filter)

@@ -57,6 +57,8 @@ class GeneratedModel:
     pattern: list = dataclasses.field(default_factory=list)
     #: compact stage image: (row, column) of each stored entry (lp, LDS image, elimination)
     compact: list = dataclasses.field(default_factory=list)
+    #: compact entries that an evaluator assigns (the rest stay zero); MPCX_LPW_INIT is their bit mask
+    lp_written: list = dataclasses.field(default_factory=list)
     #: local index of each stage row in the stage system
     crow: list = dataclasses.field(default_factory=list)
 
@@ -457,10 +459,20 @@ def generate(nlp: StageNLP, ts: float = None, _bordered=None) -> GeneratedModel:
     for ln in elim_lines + elim0_lines:
         used_pk.update(int(m.group(1)) for m in re.finditer(r"F\[(\d+)\]", ln))
     unpk = {pk(i, j): (i, j) for i in range(n_img) for j in range(i + 1)}
+    # The entries some evaluator assigns (Jacobian and Hessian bodies; their network variants emit
+    # the same assignments) against those that stay the zeros the kernel's init stored: fill, dual
+    # diagonals, Hessian diagonals without a term.  The free tail -- what follows the diagonal and
+    # the border, reached only through the index tables -- holds the written entries first, so the
+    # Newton assembly loads one contiguous run of it and takes 0.0 for the rest (MPCX_LPW_INIT).
+    written_pk = {int(m.group(1)) for ln in gj_lines + h_lines for m in re.finditer(r"\blp\[(\d+)\]\s*=", ln)}
     compact = [(i, i) for i in range(n_img)] + [(nloc, j) for j in range(nloc)]
     head = {pk(i, j) for i, j in compact}
-    compact += [unpk[t] for t in sorted(used_pk - head)]
+    tail = sorted(used_pk - head)
+    compact += [unpk[t] for t in tail if t in written_pk] + [unpk[t] for t in tail if t not in written_pk]
     cix = {pk(i, j): c for c, (i, j) in enumerate(compact)}
+    lp_written = sorted(cix[t] for t in written_pk)
+    lpw_words = [sum(1 << (c - 64 * w) for c in lp_written if 64 * w <= c < 64 * (w + 1))
+                 for w in range((len(compact) + 63) // 64)]
 
     def to_compact(lines, arr):
         # lp (the evaluators' image in HBM) is stage-minor: entry c of the stage at lp[c * S]
@@ -500,6 +512,7 @@ def generate(nlp: StageNLP, ts: float = None, _bordered=None) -> GeneratedModel:
         f"#define MPCX_NCPT {len(compact)}",
         f"#define MPCX_CPK_INIT {', '.join(str(pk(i, j)) for i, j in compact)}",
         f"#define MPCX_CIJ_INIT {', '.join(str(i | (j << 8)) for i, j in compact)}",
+        f"#define MPCX_LPW_INIT {', '.join(f'0x{w:x}ull' for w in lpw_words)}",
         *(["#define MPCX_FORCE_BLOCK_CHAIN 1"] if force_chain else []),
         *([f"#define MPCX_NMU {nmu}",
            f"#define MPCX_CROW_INIT {', '.join(map(str, crow))}",
@@ -570,4 +583,4 @@ def generate(nlp: StageNLP, ts: float = None, _bordered=None) -> GeneratedModel:
     key = hashlib.sha1(src.encode()).hexdigest()[:16]
     return GeneratedModel(source=src, key=key, dims=dims, flops=flops, nnz=nnz, block_chain_only=force_chain,
                           bordered_rows=list(bordered), elim=elim_plan, elim_lines=elim_lines, pattern=P,
-                          compact=compact, crow=crow, elim0=elim0_plan, elim0_lines=elim0_lines)
+                          compact=compact, lp_written=lp_written, crow=crow, elim0=elim0_plan, elim0_lines=elim0_lines)

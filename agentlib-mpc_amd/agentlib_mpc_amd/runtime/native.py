@@ -315,10 +315,12 @@ def _kernel_deps_hash() -> str:
     return h.hexdigest()[:10]
 
 
-def _extra_defines() -> List[str]:
+def _extra_defines(defines: Optional[str] = None) -> List[str]:
     """Diagnostic kernel variants: ``MPCX_DEFINES="A,B=1"`` adds ``-DA -DB=1`` (e.g.
-    ``MPCX_NO_STATIC`` forces the dense Bunch-Kaufman path); part of the code-object name."""
-    return [d for d in os.environ.get("MPCX_DEFINES", "").split(",") if d]
+    ``MPCX_NO_STATIC`` forces the dense Bunch-Kaufman path); part of the code-object name.
+    ``defines``: the value to use instead of the environment's (builds started side by side)."""
+    text = os.environ.get("MPCX_DEFINES", "") if defines is None else defines
+    return [d for d in text.split(",") if d]
 
 
 #: small-fleet variant (workspace in LDS, one agent per CU; ``mpcx_problem_small_fleet``)
@@ -369,19 +371,20 @@ VARIANTS = (
 _BY_KEY = {v.key: v for v in VARIANTS}
 
 
-def code_object_path(gen_key: str, variant: Optional[str] = None) -> pathlib.Path:
-    extra = _extra_defines()
+def code_object_path(gen_key: str, variant: Optional[str] = None, defines: Optional[str] = None) -> pathlib.Path:
+    extra = _extra_defines(defines)
     tag = ("_" + hashlib.sha1(",".join(extra).encode()).hexdigest()[:6]) if extra else ""
     vtag = f"_{variant}" if variant else ""
     return KERNEL_DIR / f"mpcx_{gen_key}_{_kernel_deps_hash()}{tag}{vtag}_{OFFLOAD_ARCH}.hsaco"
 
 
-def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> Optional[pathlib.Path]:
+def compile_model(gen, verbose: bool = False, variant: Optional[str] = None,
+                  defines: Optional[str] = None) -> Optional[pathlib.Path]:
     """Compile a generated model source to a gfx950 code object (cached).  ``variant``
     SMALL_FLEET: the workspace-in-LDS build; None (and a ``.nofit`` marker) when the
     structure's workspace does not fit a CU's LDS."""
     KERNEL_DIR.mkdir(parents=True, exist_ok=True)
-    out = code_object_path(gen.key, variant)
+    out = code_object_path(gen.key, variant, defines)
     if out.exists():
         return out
     nofit = out.with_suffix(".nofit")
@@ -389,7 +392,7 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
         return None
     v = _BY_KEY[variant] if variant is not None else None
     if v is not None and v.main_occ is not None:
-        base = compile_model(gen, verbose)
+        base = compile_model(gen, verbose, defines=defines)
         occ = base.with_suffix(".occ")
         if not occ.exists():
             # the main build's occupancy is unknown (its resource remark was not found): no
@@ -403,7 +406,7 @@ def compile_model(gen, verbose: bool = False, variant: Optional[str] = None) -> 
     src = out.with_suffix(".hip")
     src.write_text(gen.source)
     tmp = out.with_suffix(".tmp")
-    defs = _extra_defines() + list(v.defines if v is not None else ())
+    defs = _extra_defines(defines) + list(v.defines if v is not None else ())
     cmd = [_hipcc(), "--genco", f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17",
            f"-I{INCLUDE}", f"-I{CSRC}", *[f"-D{d}" for d in defs], str(src), "-o", str(tmp),
            "-Rpass-analysis=kernel-resource-usage"]

@@ -145,6 +145,38 @@ constexpr int CB = NLOC + 1;              // first border entry
 static_assert(NCPT >= CB + NLOC, "compact image holds the diagonal and the border row");
 __constant__ unsigned short kCPK[NCPT] = {MPCX_CPK_INIT};
 __constant__ unsigned short kCIJ[NCPT] = {MPCX_CIJ_INIT};
+// The image entries some generated evaluator assigns, one bit per entry (MPCX_LPW_INIT, 64-bit words):
+// every other entry of lp stays the zero init_agent stored -- elimination fill, dual diagonals (the
+// assembly overwrites them), Hessian diagonals without a term, the border (taken from the rhs) -- so
+// the Newton assembly takes 0.0 for it instead of loading it; codegen puts the written entries of the
+// free tail first, which leaves the unwritten ones in lines of their own.  MPCX_LP_ALL (diagnostics,
+// A/B) or a source without the mask: every entry is loaded, as before.
+constexpr int LPW_WORDS = (NCPT + 63) / 64;
+#if defined(MPCX_LPW_INIT) && !defined(MPCX_LP_ALL)
+constexpr bool LP_MASKED = true;
+__host__ __device__ constexpr unsigned long long lpw_word(int q) {
+  constexpr unsigned long long w[LPW_WORDS] = {MPCX_LPW_INIT};
+  return w[q];
+}
+#else
+constexpr bool LP_MASKED = false;
+__host__ __device__ constexpr unsigned long long lpw_word(int) { return ~0ull; }
+#endif
+template <int Q> struct LpwWord { static constexpr unsigned long long v = lpw_word(Q); };
+template <int Q = 0>
+__device__ __forceinline__ unsigned long long lpw_sel(int q) {  // word q, selected among immediates
+  if constexpr (Q + 1 >= LPW_WORDS) return LpwWord<Q>::v;
+  else return q == Q ? LpwWord<Q>::v : lpw_sel<Q + 1>(q);
+}
+__device__ __forceinline__ bool lp_written(int t) { return !LP_MASKED || ((lpw_sel(t >> 6) >> (t & 63)) & 1ull) != 0ull; }
+// a written entry (0 when there is none): where the load of an unwritten one is sent, so that it stays
+// unconditional (no branch, no wait inside one) and fetches no line of its own
+__host__ __device__ constexpr int lpw_first() {
+  for (int t = 0; t < NCPT; ++t)
+    if ((lpw_word(t >> 6) >> (t & 63)) & 1ull) return t;
+  return 0;
+}
+constexpr int LPW_ANY = lpw_first();
 
 // workspace layout (doubles per agent)
 constexpr long O_X = 0, O_S = O_X + NW, O_LAM = O_S + M, O_ZL = O_LAM + M, O_ZU = O_ZL + NW;
@@ -273,6 +305,11 @@ struct KState {
   // (bar_ok): recover_step then takes it instead of recomputing every log of the slacks
   double bar_val;
   int bar_ok;
+  // 1: the accepted-point pass of the last regular step already evaluated this iterate's Hessian
+  // (eval_hess_lds, sigma = obj_scale).  The main loop's eval_hess site takes and clears it on every
+  // pass, so an iterate reached any other way -- the first one, a soft step, the start of, the
+  // iterations of and the return from a restoration phase -- finds it clear and evaluates.
+  int hess_ok;
   double sw_l, sw_r;          // the line search's switching-condition powers (loop invariant)
 };
 
@@ -280,9 +317,13 @@ struct KState {
 #define MPCX_NETX 0
 #define MPCX_NETO 0
 #endif
-// everything in LDS except the phase-shared union
-struct LdsRest {
+// everything in LDS except the phase-shared union; NGSL: the length of the resident constraint scaling
+// (gsl), chosen per build below (GS_RES): M, or 0 -- an empty array (a compiler extension), so that a
+// build without the copy keeps every offset and the size it had
+template <int NGSL>
+struct LdsRestT {
   double par[NPAR];        // agent parameters (read by every evaluation)
+  double gsl[NGSL];        // the constraint scaling gs (GS_RES)
   double S[N * SOFF];      // local Schur blocks per stage: S00 (x_k), S11 (c_k), S10 (c_k x x_k)
   double Dinv[N * NCC];    // inverses of the chain pivots
   double zx[N * (NX + NCP)];  // forward-eliminated rhs of (x_k, c_k) per stage
@@ -343,10 +384,10 @@ struct TrialLds {
 // LDS budget (one wavefront per workgroup, 160 KB per CU): the most agents per CU for which
 // the fixed part plus a minimal union fits -- all N compact stage images in one round if
 // that still gives >= 4 agents per CU, else at least two images per round -- and the
-// static rounds / dense images take what is left of that share.
+// static rounds / dense images take what is left of that share.  Everything here follows from
+// the fixed part's size (lds_plan), so that it can be worked out for two candidate layouts.
 constexpr int SLOT_BYTES = 8 * PKS + 8 * NI;  // dense packed system + perm/piv (fallback)
 constexpr int CSLOT_BYTES = 8 * NCS;          // compact image (static elimination)
-constexpr int REST_BYTES = (int)sizeof(LdsRest);
 constexpr int UFIX_BYTES = cmax((int)sizeof(SeqLds), cmax(8 * N * NB, (int)sizeof(TrialLds)));
 constexpr int LDS_CU_ALL = 163840, LDS_SLACK = 256;
 #ifdef MPCX_WS_LDS
@@ -366,33 +407,79 @@ constexpr int K0 = 1;
 constexpr int K0 = 0;
 #endif
 constexpr int NRS = N - K0;                         // stages in the regular rounds
-constexpr int APC_ONE = apc_for(REST_BYTES + cmax(UFIX_BYTES, cmax(SLOT_BYTES, cmax(NRS, 1) * CSLOT_BYTES)));
-constexpr int APC_TWO = apc_for(REST_BYTES + cmax(UFIX_BYTES, cmax(SLOT_BYTES, cmin(cmax(NRS, 1), 2) * CSLOT_BYTES)));
+struct LdsPlan {
+  int apc;       // agents per CU
+  int budget;    // bytes per agent
+  int crounds;   // static rounds
+  int src;       // compact images per static round
+  int sr;        // dense images per dense round
+  int ubytes;    // size of the phase-shared union
+  bool fits;     // fixed part + union inside the agent's share
+};
+__host__ __device__ constexpr LdsPlan lds_plan(int rest) {
+  LdsPlan p{};
+  const int apc_one = apc_for(rest + cmax(UFIX_BYTES, cmax(SLOT_BYTES, cmax(NRS, 1) * CSLOT_BYTES)));
+  const int apc_two = apc_for(rest + cmax(UFIX_BYTES, cmax(SLOT_BYTES, cmin(cmax(NRS, 1), 2) * CSLOT_BYTES)));
 #ifdef MPCX_WS_LDS
-static_assert(WS_LDS_BYTES + REST_BYTES + UFIX_BYTES + LDS_SLACK <= LDS_CU_ALL, "MPCX_WS_LDS: workspace does not fit LDS");
-constexpr int APC = 1;
+  p.apc = 1;
 #elif defined(MPCX_APC)  // agents per CU chosen by the build (more than 16: 5-8 waves per SIMD)
-constexpr int APC = MPCX_APC;
+  p.apc = MPCX_APC;
 #else
-constexpr int APC = (APC_TWO >= 16 || APC_ONE < 4) ? APC_TWO : APC_ONE;
+  p.apc = (apc_two >= 16 || apc_one < 4) ? apc_two : apc_one;
 #endif
 #ifdef MPCX_LDS_TARGET_OVERRIDE  // diagnostics (scripts/variants.py): per-agent byte budget
-constexpr int LDS_BUDGET = MPCX_LDS_TARGET_OVERRIDE;
+  p.budget = MPCX_LDS_TARGET_OVERRIDE;
 #else
-constexpr int LDS_BUDGET = LDS_CU / APC - LDS_SLACK;
+  p.budget = LDS_CU / p.apc - LDS_SLACK;
 #endif
-// static path: SRC compact images per round, one lane eliminates a stage, GC lanes assemble it.
-// A model whose stage 0 opens rows that are equalities later on (MHE) has a second plan for
-// stage 0 (gen_stage_elim0), run in a round of its own after stages K0.. so that no round
-// executes both bodies divergently.
-constexpr int SRC0 = cmax(1, cmin(cmin(cmax(NRS, 1), WAVE), (LDS_BUDGET - REST_BYTES) / CSLOT_BYTES));
-constexpr int CROUNDS = (NRS + SRC0 - 1) / SRC0;
-constexpr int SRC = CROUNDS > 0 ? (NRS + CROUNDS - 1) / CROUNDS : 1;  // stages per round (balanced)
+  // static path: SRC compact images per round, one lane eliminates a stage, GC lanes assemble it.
+  // A model whose stage 0 opens rows that are equalities later on (MHE) has a second plan for
+  // stage 0 (gen_stage_elim0), run in a round of its own after stages K0.. so that no round
+  // executes both bodies divergently.
+  const int src0 = cmax(1, cmin(cmin(cmax(NRS, 1), WAVE), (p.budget - rest) / CSLOT_BYTES));
+  p.crounds = (NRS + src0 - 1) / src0;
+  p.src = p.crounds > 0 ? (NRS + p.crounds - 1) / p.crounds : 1;  // stages per round (balanced)
+  // dense Bunch-Kaufman path (stages the static plan rejects): SR dense images per round
+  const int sr0 = cmax(1, cmin(cmin(N, WAVE), (p.budget - rest) / SLOT_BYTES));
+  const int rounds = (N + sr0 - 1) / sr0;
+  p.sr = (N + rounds - 1) / rounds;   // stages per round (balanced)
+  p.ubytes = cmax(UFIX_BYTES, cmax(p.sr * SLOT_BYTES, p.src * CSLOT_BYTES));
+  p.ubytes = (p.ubytes + 7) / 8 * 8;
+  p.fits = rest + p.ubytes <= p.budget;
+  return p;
+}
+// The constraint scaling gs never changes after init_agent, and every hot phase that touches a row
+// reads it (the iteration head, both halves of a line-search trial, the uncached step recovery, both
+// derivative passes).  Where a copy of it fits into LDS without moving what the build's speed rests on
+// -- agents per CU, the static rounds and their images per round, the resident Newton step, the share
+// itself -- those phases read the copy (gs_at, gs_stage); the workspace's gs stays for the cold paths
+// (restoration phase, block chain, outputs).  The dense fallback may get fewer images per round from
+// it (four structures of the catalogue: one fewer): each stage is factored on its own, so a round's size changes no
+// result.  The small-fleet build's workspace is in LDS already.  MPCX_GS_HBM (diagnostics, A/B):
+// every reader loads the workspace's gs, as before.
+__host__ __device__ constexpr bool gs_res_ok() {
+#if defined(MPCX_WS_LDS) || defined(MPCX_GS_HBM)
+  return false;
+#else
+  const LdsPlan p0 = lds_plan((int)sizeof(LdsRestT<0>)), p1 = lds_plan((int)sizeof(LdsRestT<MM>));
+  const bool step0 = 8 * N * NB + (int)sizeof(TrialLds) <= p0.ubytes;
+  const bool step1 = 8 * N * NB + (int)sizeof(TrialLds) <= p1.ubytes;
+  return M > 1 && p1.fits && p1.apc == p0.apc && p1.crounds == p0.crounds && p1.src == p0.src && step1 == step0;
+#endif
+}
+constexpr bool GS_RES = gs_res_ok();
+using LdsRest = LdsRestT<GS_RES ? MM : 0>;
+constexpr int REST_BYTES = (int)sizeof(LdsRest);
+constexpr LdsPlan PLAN = lds_plan(REST_BYTES);
+#ifdef MPCX_WS_LDS
+static_assert(WS_LDS_BYTES + REST_BYTES + UFIX_BYTES + LDS_SLACK <= LDS_CU_ALL, "MPCX_WS_LDS: workspace does not fit LDS");
+#endif
+constexpr int APC = PLAN.apc;
+constexpr int LDS_BUDGET = PLAN.budget;
+constexpr int CROUNDS = PLAN.crounds;
+constexpr int SRC = PLAN.src;
 constexpr int GC = pow2floor(WAVE / SRC);          // lanes per stage (assembly)
-// dense Bunch-Kaufman path (stages the static plan rejects): SR dense images per round
-constexpr int SR0 = cmax(1, cmin(cmin(N, WAVE), (LDS_BUDGET - REST_BYTES) / SLOT_BYTES));
-constexpr int ROUNDS = (N + SR0 - 1) / SR0;
-constexpr int SR = (N + ROUNDS - 1) / ROUNDS;   // stages per round (balanced)
+constexpr int SR = PLAN.sr;
 constexpr int G = pow2floor(WAVE / SR);         // lanes per stage
 
 struct ParLds {
@@ -416,6 +503,7 @@ union LinLds {
 struct Lds : LdsRest {
   LinLds u;
 };
+static_assert(sizeof(LinLds) == PLAN.ubytes, "lds_plan sizes the union as the compiler does");
 #ifndef MPCX_LDS_TARGET_OVERRIDE
 static_assert(sizeof(Lds) + LDS_SLACK <= LDS_CU / APC, "LDS share per agent exceeded");
 #endif
@@ -444,6 +532,24 @@ __shared__ Lds gL;  // one agent per workgroup: the agent's LDS scratch
 constexpr bool STEP_RES = 8 * N * NB + sizeof(TrialLds) <= sizeof(LinLds);
 #else
 constexpr bool STEP_RES = false;
+#endif
+// The hand-off from the acceptance to the derivative passes (the kernel's main loop, accept_step):
+// MPCX_LAM_HBM (diagnostics, A/B): the stage lanes load the accepted multipliers from the workspace,
+// behind a full barrier; MPCX_HESS_PHASE (diagnostics, A/B): the Hessian is evaluated by the phase of
+// its own after the next iteration head.  The small-fleet build keeps the phase: its workspace is LDS,
+// so the phase's operand loads were never a memory round trip and its call is inlined already -- the
+// part has nothing to remove there.  Network models keep it too: with the network's Hessian pass on the
+// matrix cores inlined into the kernel body the NARX zone leg ran 1.2 % slower (3.02 - 3.04 ms against
+// 2.98 - 3.01 with the phase, profiles/r09/narx_switches.json).
+#ifndef MPCX_LAM_HBM
+constexpr bool LAM_RES = true;
+#else
+constexpr bool LAM_RES = false;
+#endif
+#if !defined(MPCX_HESS_PHASE) && !defined(MPCX_WS_LDS) && !defined(MPCX_NET_MFMA)
+constexpr bool HESS_FUSED = true;
+#else
+constexpr bool HESS_FUSED = false;
 #endif
 constexpr int TRIAL_OFF = STEP_RES ? 8 * N * NB : 0;  // bytes from the union's start
 static_assert(TRIAL_OFF + sizeof(TrialLds) <= sizeof(LinLds), "trial point inside the union");
@@ -562,6 +668,17 @@ struct Agent {
 #undef ws
 };
 
+// the constraint scaling for the hot phases: the LDS copy where the build has one (GS_RES), else the
+// workspace's; row c, and a stage's NG rows for the generated evaluators
+__device__ __forceinline__ double gs_at(const Agent a, int c) {
+  if constexpr (GS_RES) return gL.gsl[c];
+  else return a.gs()[c];
+}
+__device__ __forceinline__ const double* gs_stage(const Agent a, int k) {
+  if constexpr (GS_RES) return (const double*)(gL.gsl + k * NG);
+  else return (const double*)(a.gs() + k * NG);
+}
+
 // constraint classes: 0 equality, 1 inequality with a finite bound, 2 free
 __device__ __forceinline__ int cls_of(double lo, double hi, double sl, double su) {
   if (lo == hi) return 0;
@@ -678,13 +795,21 @@ __device__ __noinline__ void eval_gj_ws(const Agent a, const wdbl* xv, int full)
 // derivatives at the accepted trial point (still in LDS), with the accepted multipliers
 // inlined into the kernel body: as a leaf call it saved and restored the callee-saved VGPRs
 // its generated derivative code uses on every iteration (C3 -4 %, profiles/r03/s2/var_sgpr_c3.txt)
+// LAM_LDS: the multipliers are those accept_step<.., true> left in the trial point's gt (below);
+// else the workspace's
+template <bool LAM_LDS>
+__device__ __forceinline__ const double* lam_stage(const Agent a, int k) {
+  if constexpr (LAM_LDS) return (const double*)(trial().gt + k * NG);
+  else return (const double*)(a.lam() + k * NG);
+}
+template <bool LAM_LDS>
 __device__ __attribute__((always_inline)) void eval_gj_lds(const Agent a) {
   NET_PREP(trial().xt, gj);
   const int full = gL.want_sdh;
   for (int k = lane_now(); k < N; k += WAVE)
     STAGE_GJ((const double*)(trial().xt + k * NP), par_stage(k), par_global(), k * TS,
-             (double*)(a.sdg() + k), (double*)(a.sdj() + k), N, (const double*)(a.gs() + k * NG),
-             (double*)a.lp(k), (const double*)(a.lam() + k * NG), (double*)(a.jtl() + k), full);
+             (double*)(a.sdg() + k), (double*)(a.sdj() + k), N, gs_stage(a, k),
+             (double*)a.lp(k), lam_stage<LAM_LDS>(a, k), (double*)(a.jtl() + k), full);
 }
 
 // Hessian of sigma*f + sum lam_i * gs_i * g_i (scaled Lagrangian) into the packed
@@ -695,13 +820,37 @@ __device__ MPCX_HOT void eval_hess_impl(const Agent a, double sigma, int full) {
   for (int k = lane_now(); k < N; k += WAVE) {
     double lk[NG > 0 ? NG : 1];
 #pragma unroll
-    for (int r = 0; r < NG; ++r) lk[r] = a.lam()[k * NG + r] * a.gs()[k * NG + r];
+    for (int r = 0; r < NG; ++r) lk[r] = a.lam()[k * NG + r] * gs_at(a, k * NG + r);
     STAGE_HESS((const double*)(a.x() + k * NP), par_stage(k), par_global(), k * TS, sigma, lk,
                (double*)(a.sdh() + k), N, (double*)a.lp(k), full);
   }
   if (lane_now() == 0) { gL.hsig = sigma; gL.sdh_ok = full; }
 }
 __device__ __forceinline__ void eval_hess(const Agent a, double sigma) { eval_hess_impl(a, sigma, gL.want_sdh); }
+
+// The same Hessian at the accepted trial point, run by the stage lanes right after eval_gj_lds: the
+// regular iteration's eval_hess evaluates at exactly this point (accept_step stores xt to x for every
+// free variable and xt equals x for the others; lam is what lam_stage reads), so its operand loads,
+// its call and its memory round trip go (KState::hess_ok).  It writes other image entries than the
+// Jacobian pass (primal x primal against dual x primal); the scheduling barrier keeps the two
+// generated bodies apart.  The strided full Hessians are not written here: the caller leaves an agent
+// that wants them (the block chain in use) to the phase.
+template <bool LAM_LDS>
+__device__ __attribute__((always_inline)) void eval_hess_lds(const Agent a, double sigma) {
+  __builtin_amdgcn_sched_barrier(0);
+  NET_PREP(trial().xt, hess);
+  constexpr int full = 0;
+  for (int k = lane_now(); k < N; k += WAVE) {
+    double lk[NG > 0 ? NG : 1];
+    const double* lm = lam_stage<LAM_LDS>(a, k);
+    const double* g = gs_stage(a, k);
+#pragma unroll
+    for (int r = 0; r < NG; ++r) lk[r] = lm[r] * g[r];
+    STAGE_HESS((const double*)(trial().xt + k * NP), par_stage(k), par_global(), k * TS, sigma, lk,
+               (double*)(a.sdh() + k), N, (double*)a.lp(k), full);
+  }
+  if (lane_now() == 0) { gL.hsig = sigma; gL.sdh_ok = full; }
+}
 
 // gradient of the (unscaled) objective w.r.t. w[i], i >= NX (stage derivatives of
 // stage b and, for a state, the X0 part of stage b+1)
@@ -1083,12 +1232,15 @@ __device__ MPCX_HOT void local_assemble(const Agent a, int k, int g, ldsd* F, co
   for (int e0 = 0; e0 < EPC; e0 += CH) {
     double v[CH], dv[CH];
     int ijv[CH];
+    bool zr[CH];  // an entry no evaluator writes: 0.0 (its load goes to a written entry's address)
 #pragma unroll
     for (int e = 0; e < CH; ++e) {
       const int t = g + (e0 + e) * GG;
       // border (rhs) entries from the rhs the rhs phases wrote in block order; x_k has none
       const bool bd = t >= CB && t < CB + NLOC && lkind(t - CB) != 2;
-      v[e] = bd ? rb[lblk(t - CB, lkind(t - CB))] : src[(t < NCPT ? t : 0) * N];
+      const int tc = t < NCPT ? t : 0;
+      zr[e] = !bd && !lp_written(tc);
+      v[e] = bd ? rb[lblk(t - CB, lkind(t - CB))] : src[(zr[e] ? LPW_ANY : tc) * N];
       dv[e] = dg[t < NLOC ? t : 0];
       // the entry's (row, column) with the image loads, not under the fixed-entry branch below:
       // kCIJ is a global-memory table, and a load waited for inside a divergent branch drains
@@ -1099,7 +1251,7 @@ __device__ MPCX_HOT void local_assemble(const Agent a, int k, int g, ldsd* F, co
     for (int e = 0; e < CH; ++e) {
       const int t = g + (e0 + e) * GG;
       if (e0 + e >= EPC || t >= NCPT) continue;
-      double x = v[e];
+      double x = zr[e] ? 0.0 : v[e];
       bool fix = false;
       if (fm != 0ull) {
         const int ij = ijv[e], i = ij & 255, j = ij >> 8;
@@ -1761,7 +1913,8 @@ __device__ __forceinline__ void assemble_reg(const Agent a, int k, const KKTDiag
   for (int t = 0; t < NCPT; ++t) {
     // border (rhs) entries from the rhs the rhs phases wrote in block order; x_k has none
     const bool bd = t >= CB && t < CB + NLOC && lkind(t - CB) != 2;
-    Fr[t] = bd ? rb[lblk(t - CB, lkind(t - CB))] : src[t * N];
+    // t is a constant here: an entry no evaluator writes is 0.0 without a load
+    Fr[t] = bd ? rb[lblk(t - CB, lkind(t - CB))] : lp_written(t) ? src[t * N] : 0.0;
   }
   if (fm != 0ull) {
 #pragma unroll
@@ -2086,7 +2239,9 @@ __device__ __noinline__ Scal init_agent(const Agent a, int agent) {
     double rm = 0.0;
     for (int j = 0; j < NL; ++j)
       if (a.xL()[k * NP + j] != a.xU()[k * NP + j]) rm = fmax(rm, fabs(a.sdj()[(r * NL + j) * N + k]));
-    a.gs()[c] = (rm > o.nlp_scaling_max_gradient) ? fmax(o.nlp_scaling_min_value, o.nlp_scaling_max_gradient / rm) : 1.0;
+    const double gsc = (rm > o.nlp_scaling_max_gradient) ? fmax(o.nlp_scaling_min_value, o.nlp_scaling_max_gradient / rm) : 1.0;
+    a.gs()[c] = gsc;
+    if constexpr (GS_RES) gL.gsl[c] = gsc;  // final: the hot phases' copy (the barriers below publish it)
   }
   // bound relaxation + initial point
   for (int i = lane; i < NW; i += WAVE) {
@@ -2372,7 +2527,7 @@ __device__ MPCX_HOT StepInfo recover_step(const Agent a, double mu, double tau, 
     vl[sl] = a.vL()[sq[sl]]; vu[sl] = a.vU()[sq[sl]];
     // theta_cached: the accepted trial summed the same terms (line_search), so its operands stay unloaded
     lbv[sl] = 0.0; gvv[sl] = 0.0; gsc[sl] = 0.0;
-    if (!theta_cached) { lbv[sl] = a.lb()[cc]; gvv[sl] = a.gv()[cc]; gsc[sl] = a.gs()[cc]; }
+    if (!theta_cached) { lbv[sl] = a.lb()[cc]; gvv[sl] = a.gv()[cc]; gsc[sl] = gs_at(a, cc); }
     dlam[sl] = gL.u.sol[(cc / NG) * NB + NP + cc % NG];
   }
 #pragma unroll
@@ -2515,7 +2670,7 @@ __device__ MPCX_HOT void line_search(const Agent a) {
 #pragma unroll
     for (int sl = 0; sl < CS; ++sl) {
       const int c = lane + sl * WAVE, cc = c < M ? c : 0, q = sidx_slot(cw, sl);
-      gsv[sl] = a.gs()[cc]; lbv[sl] = a.lb()[cc]; slv[sl] = a.sL()[q]; suv[sl] = a.sU()[q];
+      gsv[sl] = gs_at(a, cc); lbv[sl] = a.lb()[cc]; slv[sl] = a.sL()[q]; suv[sl] = a.sU()[q];
       sv[sl] = a.s()[q]; dsv[sl] = a.ds()[q];
     }
 #pragma unroll
@@ -2582,7 +2737,11 @@ __device__ MPCX_HOT void line_search(const Agent a) {
 
 // take the last trial point (xt, gt in LDS) and the multiplier steps
 // RES: the step is the resident Newton solution (STEP_RES; the restoration phase passes its workspace step)
-template <bool RES>
+// PARK: the new multipliers also go to the trial point's gt, row for row.  The lane that stores lam[c]
+// has just taken gt[c] for gv (the slot's last reader), so the slot is free, and the stage lanes of the
+// accepted-point pass (eval_gj_lds<true>, eval_hess_lds<true>) read their NG multipliers from LDS
+// instead of waiting for this phase's stores to come back from the workspace.
+template <bool RES, bool PARK = false>
 __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, double mu, double alpha, double az) {
   const int lane = lane_now();
   const double ksm = kappa_sigma * mu, mks = mu * MPCX_RCP(kappa_sigma);  // the kappa_sigma safeguard's bounds x s
@@ -2645,8 +2804,10 @@ __device__ MPCX_HOT void accept_step(const Agent a, const double kappa_sigma, do
   for (int sl = 0; sl < CS; ++sl) {
     const int c = lane + sl * WAVE;
     if (c >= M) continue;
-    a.lam()[c] = lm[sl] + alpha * dl[sl];
+    const double ln = lm[sl] + alpha * dl[sl];
+    a.lam()[c] = ln;
     a.gv()[c] = gt[sl];
+    if constexpr (PARK) trial().gt[c] = ln;
     const int cl = cls_slot(cw, sl);
     if (cl == 0) continue;  // no slack
     const double sn = sold[sl] + alpha * dsv[sl];
@@ -2721,7 +2882,7 @@ __device__ __attribute__((always_inline)) int iter_head(const Agent a) {
     for (int sl = 0; sl < CS; ++sl) {
       const int c = lane + sl * WAVE;
       const int cc = c < M ? c : 0, q = sidx_slot(cw, sl);
-      lb_[sl] = a.lb()[cc]; sl_[sl] = a.sL()[q]; su_[sl] = a.sU()[q]; gs_[sl] = a.gs()[cc]; lm_[sl] = a.lam()[cc];
+      lb_[sl] = a.lb()[cc]; sl_[sl] = a.sL()[q]; su_[sl] = a.sU()[q]; gs_[sl] = gs_at(a, cc); lm_[sl] = a.lam()[cc];
       gv_[sl] = a.gv()[cc]; sv_[sl] = a.s()[q]; vl_[sl] = a.vL()[q]; vu_[sl] = a.vU()[q];
     }
 #pragma unroll
@@ -3027,7 +3188,7 @@ __device__ __noinline__ int soft_try(const Agent a) {
   const double pd0 = pd_error(a, K.mu, K.obj_scale);
   iterate_copy(a, 1);
   soft_apply(a, K.mu, K.ls.alpha);
-  eval_gj_lds(a);
+  eval_gj_lds<false>(a);
   sync();
   const double pd1 = pd_error(a, K.mu, K.obj_scale);
   if (pd1 <= SOFT_PD_FACTOR * pd0) {
@@ -3868,7 +4029,7 @@ __device__ __noinline__ int resto_tail(const Agent a) {
   wsync();
   accept_step_resto(a, (*argp).opt.kappa_sigma, K.mu, ls.alpha, K.st.az);
   sync();
-  eval_gj_lds(a);
+  eval_gj_lds<false>(a);
   sync();
   K.it += 1;
   K.n_resto_it += 1;
@@ -3994,6 +4155,7 @@ extern "C" __global__ void __launch_bounds__(64, MIN_WAVES) mpcx_ipm_solve(Args 
   K.resto = 0; K.soft = 0; K.soft_count = 0; K.lsmode = 0; K.n_soft = 0; K.n_resto_it = 0;
   K.n_filt_over = 0; K.n_refine = 0;
   K.bar_ok = 0; K.bar_val = 0.0;
+  K.hess_ok = 0;
 #define KARGP ((KArgs*)__builtin_amdgcn_kernarg_segment_ptr())
 #pragma unroll 1
   for (;;) {
@@ -4020,7 +4182,13 @@ extern "C" __global__ void __launch_bounds__(64, MIN_WAVES) mpcx_ipm_solve(Args 
     }
     if (!K.resto && iter_head(a)) break;  // one (inlined) call site
     PROF(2);
-    eval_hess(a, K.resto ? 0.0 : K.obj_scale);  // restoration: the constraints' curvature only
+    {
+      // the regular step's accepted-point pass evaluated it already (one evaluation per solve is
+      // wasted: the one before the head that stops)
+      const int have = HESS_FUSED ? K.hess_ok : 0;
+      if constexpr (HESS_FUSED) K.hess_ok = 0;
+      if (!have) eval_hess(a, K.resto ? 0.0 : K.obj_scale);  // restoration: the constraints' curvature only
+    }
     PROF(3);
     // factorisation with inertia correction (IPOPT Algorithm IC); in the restoration phase the
     // same loop then re-factors for the iterative-refinement corrections (one factor() call
@@ -4126,11 +4294,26 @@ extern "C" __global__ void __launch_bounds__(64, MIN_WAVES) mpcx_ipm_solve(Args 
     K.fx = K.ls.tr.f;
     wsync();
     PROF(8);
-    accept_step<STEP_RES>(a, OPT(kappa_sigma), K.mu, K.ls.alpha, mode == 1 ? K.ls.alpha : K.st.az);
+    accept_step<STEP_RES, LAM_RES>(a, OPT(kappa_sigma), K.mu, K.ls.alpha, mode == 1 ? K.ls.alpha : K.st.az);
     K.bar_val = K.ls.bar;        // the new iterate IS the last trial point: its barrier sum holds
     K.bar_ok = 1;
-    sync();  // accepted multipliers visible to the stage lanes
-    eval_gj_lds(a);
+    // The accepted-point pass: the stage lanes' Jacobian pass and, unless MPCX_HESS_PHASE, the next
+    // iteration's Hessian.  With the multipliers parked in LDS (LAM_RES) it loads nothing that the
+    // acceptance stored to the workspace -- the point and the multipliers come from the trial point's
+    // LDS, the parameters and (GS_RES) the scaling from LDS too; without GS_RES it loads gs, which no
+    // phase after init_agent stores -- so the lanes only have to see each other's LDS stores (wsync).
+    // What the acceptance stored is read again by the iteration head: x, z, lam, gv, s and v by the
+    // lane that stored them; every cross-lane reader (the head's gradient sums, the factorisation,
+    // the step recovery) comes after the sync() below, which also publishes this pass's stores.
+    if constexpr (LAM_RES) wsync();
+    else sync();  // accepted multipliers visible to the stage lanes
+    eval_gj_lds<LAM_RES>(a);
+    if constexpr (HESS_FUSED) {
+      if (!gL.want_sdh) {  // (wave-uniform) the block chain's strided Hessians: the phase writes them
+        eval_hess_lds<LAM_RES>(a, K.obj_scale);
+        K.hess_ok = 1;
+      }
+    }
     sync();
     K.it += 1;
     PROF(9);
