@@ -7,6 +7,8 @@
 * ``exchange_supply`` C4 supply agent — `examples/exchange_admm/configs/rlt_admm.json`
 * ``room_nn``         C5 zone agent (NARX ANNs) — `examples/three_zone_datadriven_admm/configs/mpc/Room_1.json`
 * ``mhe_room``        moving horizon estimator — `examples/Estimators/mhe_example.py:188-228`
+* ``one_room_cia``    on / off cooler, backend ``casadi_cia`` —
+  `examples/one_room_mpc/physical/mixed_integer/mixed_integer_mpc_cia.py:142-183`
 
 Each builder returns ``(backend, current_vars)`` with the example's values;
 keyword arguments override the per-agent values used for synthetic fleets.
@@ -21,7 +23,7 @@ import os
 import numpy as np
 
 from agentlib_mpc_amd.data_structures import admm_datatypes as adt
-from agentlib_mpc_amd.data_structures.mpc_datamodels import MPCVariable, VariableReference
+from agentlib_mpc_amd.data_structures.mpc_datamodels import MINLPVariableReference, MPCVariable, VariableReference
 from agentlib_mpc_amd.optimization_backends import create_optimization_backend
 
 #: parity settings: a tight tolerance and no acceptable-level stop, so that two solvers are
@@ -57,6 +59,33 @@ def one_room(N=15, T0=298.16, load=150.0, T_in=290.15, T_upper=295.15, u_prev=0.
     }
     if r_delta_mDot is not None:
         cv["r_delta_mDot"] = V("r_delta_mDot", r_delta_mDot)
+    return be, cv
+
+
+def one_room_cia(N=10, T0=298.16, load=150.0, T_in=290.15, T_upper=295.15, s_T=3.0, r_cooling=1 / 3,
+                 cooler_mod_limit=250.0, d=2, solver_options=REFERENCE, model=None, **config):
+    """The on / off cooler room on the CIA backend, with the example's values.  The relaxed problem
+    is degenerate where the switch goes to 0 (both big-M rows and the power's bound meet): it is
+    solved with the reference's solver settings, not ``TIGHT``.  ``config``: further backend
+    config entries (results file ...)."""
+    be = create_optimization_backend({
+        "type": "mi355x_cia",
+        "model": model or {"type": "agentlib_mpc_amd.models.examples.CoolerRoom"},
+        "discretization_options": {"collocation_order": d, "collocation_method": "legendre",
+                                   "prediction_horizon": N, "time_step": 300},
+        "solver": {"name": "ipopt", "options": solver_options},
+        **config,
+    })
+    be.setup_optimization(MINLPVariableReference(
+        states=["T"], controls=["cooling_power"], binary_controls=["cooler_on"],
+        inputs=["load", "T_upper", "T_in"], parameters=["s_T", "r_cooling", "cooler_mod_limit"], outputs=[]))
+    cv = {
+        "T": V("T", T0, 288.15, 303.15), "cooling_power": V("cooling_power", 250.0, 0.0, 500.0),
+        "cooler_on": V("cooler_on", 0.0, 0.0, 1.0),
+        "load": V("load", load), "T_upper": V("T_upper", T_upper), "T_in": V("T_in", T_in),
+        "s_T": V("s_T", s_T), "r_cooling": V("r_cooling", r_cooling),
+        "cooler_mod_limit": V("cooler_mod_limit", cooler_mod_limit),
+    }
     return be, cv
 
 
@@ -463,6 +492,7 @@ BUILDERS: Dict[str, Callable[..., Tuple[object, dict]]] = {
     "fixture_mpc": fixture_mpc,
     "fixture_admm": fixture_admm,
     "cubic_room": cubic_room,
+    "one_room_cia": one_room_cia,
 }
 
 
@@ -493,6 +523,7 @@ def compile_all(verbose: bool = False):
     for n_ in (9, 10, 19):
         variants[f"one_room_n{n_}"] = lambda n_=n_: one_room(N=n_)
     variants["one_room_n2"] = lambda: one_room(N=2)  # one stage boundary (tests/test_gpu_accepted_handoff.py)
+    variants["one_room_cia_n4"] = lambda: one_room_cia(N=4)  # tests/golden/cia_room.json
     from concurrent.futures import ThreadPoolExecutor
 
     probs = {name: fn()[0].problem for name, fn in variants.items()}

@@ -3,6 +3,7 @@
 Equations restate the reference examples:
 
 * ``OneRoom``      — `examples/one_room_mpc/physical/simple_mpc.py:27-138` (C1, C3)
+* ``CoolerRoom``   — `examples/one_room_mpc/physical/mixed_integer/mixed_integer_mpc_cia.py:28-137` (on / off cooler)
 * ``CooledRoom``   — `examples/4_Room_ADMM_Coordinator/models/room_model.py` (C2)
 * ``AirHandler``   — `examples/4_Room_ADMM_Coordinator/models/rlt_model.py` (C2)
 * ``ExchangeRoom`` — `examples/exchange_admm/models/room_model.py` (C4)
@@ -113,6 +114,49 @@ class SwitchRoom(CasadiModel):
         objective = self.create_conditional_objective((condition, objective1), default_objective=objective2)
         self.switch_test.alg = ca.if_else(self.time < self.switch.sym, 1, 2)
         return objective
+
+
+class CoolerRoomConfig(CasadiModelConfig):
+    inputs: List[CasadiInput] = [
+        _inp("cooling_power", 400, unit="W"),            # control: cooling power drawn from the zone
+        _inp("cooler_on", 1, unit="-", lb=0, ub=1),      # binary control: the cooler's on / off signal
+        _inp("load", 150, unit="W"),
+        _inp("T_in", 290.15, unit="K"),
+        _inp("T_upper", 294.15, unit="K"),
+    ]
+    states: List[CasadiState] = [
+        CasadiState(name="T", value=293.15, unit="K"),
+        CasadiState(name="T_slack", value=0, unit="K"),
+    ]
+    parameters: List[CasadiParameter] = [
+        _par("cp", 1000), _par("C", 100000), _par("s_T", 1), _par("r_cooling", 1 / 5),
+        _par("cooler_mod_limit", 200, unit="W"),  # the running cooler cannot modulate below this
+    ]
+    outputs: List[CasadiOutput] = [CasadiOutput(name="T_out", unit="K")]
+
+
+#: big-M of the on / off coupling: no cooling power above it
+COOLER_MAX_POWER = 1000
+
+
+class CoolerRoom(CasadiModel):
+    """`examples/one_room_mpc/physical/mixed_integer/mixed_integer_mpc_cia.py:28-137`: a zone cooled
+    by an on / off cooler.  Two big-M rows tie the power to the switch (off: no power; on: between
+    the modulation limit and 1000 W), the upper temperature bound is soft."""
+
+    config: CoolerRoomConfig
+
+    def setup_system(self):
+        from agentlib_mpc_amd.models.casadi_model import ca
+
+        self.T.ode = (self.load - self.cooling_power) / self.C
+        self.T_out.alg = self.T
+        self.constraints = [
+            (-ca.inf, self.cooling_power - self.cooler_on * COOLER_MAX_POWER, 0),
+            (0, self.cooling_power - self.cooler_on * self.cooler_mod_limit, ca.inf),
+            (0, self.T + self.T_slack, self.T_upper),
+        ]
+        return sum([self.r_cooling * self.cooling_power, self.s_T * self.T_slack ** 2])
 
 
 class CooledRoomConfig(CasadiModelConfig):

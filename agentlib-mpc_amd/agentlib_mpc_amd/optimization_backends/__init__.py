@@ -24,6 +24,7 @@ class BackendImport(BaseModel):
 
 _MOD = "agentlib_mpc_amd.optimization_backends.mi355x"
 _MHE = "agentlib_mpc_amd.optimization_backends.mhe"
+_CIA = "agentlib_mpc_amd.optimization_backends.cia"
 
 backend_types = {
     "mi355x": BackendImport(import_path=_MOD, class_name="MI355XBackend"),
@@ -32,6 +33,7 @@ backend_types = {
     "mi355x_ml": BackendImport(import_path=_MOD, class_name="MI355XMLBackend"),
     "mi355x_admm_ml": BackendImport(import_path=_MOD, class_name="MI355XADMMNNBackend"),
     "mi355x_mhe": BackendImport(import_path=_MHE, class_name="MHEBackend"),
+    "mi355x_cia": BackendImport(import_path=_CIA, class_name="MI355XCIABackend"),
     # drop-in aliases of the reference keys this backend replaces
     "casadi": BackendImport(import_path=_MOD, class_name="MI355XBackend"),
     "casadi_basic": BackendImport(import_path=_MOD, class_name="MI355XBaseBackend"),
@@ -41,6 +43,7 @@ backend_types = {
     "casadi_admm_ml": BackendImport(import_path=_MOD, class_name="MI355XADMMNNBackend"),
     "casadi_admm_nn": BackendImport(import_path=_MOD, class_name="MI355XADMMNNBackend"),
     "casadi_mhe": BackendImport(import_path=_MHE, class_name="MHEBackend"),
+    "casadi_cia": BackendImport(import_path=_CIA, class_name="MI355XCIABackend"),
 }
 
 uninstalled_backend_types = {}

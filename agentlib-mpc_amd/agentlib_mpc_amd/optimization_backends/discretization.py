@@ -2,8 +2,8 @@
 
 The reference transcribes with CasADi symbols in
 `casadi_/basic.py:113-392` (direct collocation, multiple shooting),
-`casadi_/full.py:36-166` (with ``u_prev``), `casadi_/admm.py:119-338` (ADMM)
-and bookkeeps through `core/discretization.py:486-595` (``add_opt_var``,
+`casadi_/full.py:36-166` (with ``u_prev``), `casadi_/admm.py:119-338` (ADMM),
+`casadi_/minlp.py:63-186` (with binary controls) and bookkeeps through `core/discretization.py:486-595` (``add_opt_var``,
 ``add_opt_par``, ``add_constraint``, ``grid``).  This module follows the same
 loops, in the same order, so the NLP vector ``w``, the parameter vector ``p``
 and the constraint vector ``g`` have exactly the reference layout (SURVEY
@@ -35,7 +35,7 @@ from agentlib_mpc_amd.data_structures.mpc_datamodels import (
     CasadiDiscretizationOptions, CollocationMethod, Integrators,
 )
 from agentlib_mpc_amd.optimization_backends.system import (
-    ADMMSystem, BaseSystem, FullSystem, OptimizationParameter, OptimizationVariable,
+    ADMMSystem, BaseSystem, FullSystem, MINLPSystem, OptimizationParameter, OptimizationVariable,
 )
 
 
@@ -742,6 +742,69 @@ class ADMMMultipleShooting(BasicMultipleShooting):
                     s.non_controlled_inputs.name: dk, s.model_parameters.name: model_pars,
                     s.penalty_factor.name: rho, s.exchange_diff.name: ed,
                     s.exchange_multipliers.name: em}
+            ode, cost, g, lb, ub = t.stage_call(s, vals, sx.ZERO)
+            x_end = self._integrate(t, s, vals, xk, ode, sx.ZERO)
+            t.pred_time = ts * (k + 1)
+            xk = t.add_opt_var(s.states)
+            t.add_constraint([sx.sub(a, b) for a, b in zip(xk, x_end)], gap_closing=True)
+            t.add_constraint(g, lb, ub)
+            t.add_cost(sx.mul(cost, ts))
+
+
+class MINLPCollocation(Discretization):
+    """`casadi_/minlp.py:63-129` (backends ``casadi_minlp`` / ``casadi_cia``, collocation): the
+    basic loop with the binary controls ``w_k`` added right after ``u_k`` and held constant over
+    the interval; the disturbances are sampled at the collocation points.
+
+    Change penalties contribute nothing on this backend, as in the reference: its loop sets
+    ``u_prev = u_k`` before it forms the penalty, so every term is zero.  None is added here."""
+
+    system_type = MINLPSystem
+
+    def _discretize(self, t, s):
+        cm = collocation_polynomial(self.options.collocation_order, self.options.collocation_method)
+        n, ts = self.options.prediction_horizon, self.options.time_step
+        x0 = t.add_opt_par(s.initial_state)
+        xk = t.add_opt_var(s.states, lb=x0, ub=x0, guess=x0)
+        const_par = t.add_opt_par(s.model_parameters)
+        for k in range(n):
+            t.block = k
+            uk = t.add_opt_var(s.controls)
+            wk = t.add_opt_var(s.binary_controls)
+            const = {s.controls.name: uk, s.model_parameters.name: const_par, s.binary_controls.name: wk}
+            x_end, cons = self._collocation_inner_loop(
+                t, s, cm, xk, [s.algebraics, s.outputs], [s.non_controlled_inputs], const)
+            t.pred_time = ts * (k + 1)
+            xk = t.add_opt_var(s.states)
+            t.add_constraint([sx.sub(a, b) for a, b in zip(xk, x_end)], gap_closing=True)
+            for c in cons:
+                t.add_constraint(*c)
+
+
+class MINLPMultipleShooting(BasicMultipleShooting):
+    """`casadi_/minlp.py:132-186` (multiple shooting): the basic loop with ``w_k`` after ``u_k``,
+    the continuity row before the model constraints.  As in the reference the stage function is
+    called without a time argument, i.e. ``time = 0``, and the loop adds no change penalties.
+    The ODE sees the binary controls like every other stage quantity."""
+
+    system_type = MINLPSystem
+
+    def _discretize(self, t, s):
+        self._check_integrator(s)
+        n, ts = self.options.prediction_horizon, self.options.time_step
+        x0 = t.add_opt_par(s.initial_state)
+        xk = t.add_opt_var(s.states, lb=x0, ub=x0, guess=x0)
+        const_par = t.add_opt_par(s.model_parameters)
+        for k in range(n):
+            t.block = k
+            uk = t.add_opt_var(s.controls)
+            wk = t.add_opt_var(s.binary_controls)
+            dk = t.add_opt_par(s.non_controlled_inputs)
+            zk = t.add_opt_var(s.algebraics)
+            yk = t.add_opt_var(s.outputs)
+            vals = {s.states.name: xk, s.algebraics.name: zk, s.outputs.name: yk,
+                    s.controls.name: uk, s.binary_controls.name: wk,
+                    s.non_controlled_inputs.name: dk, s.model_parameters.name: const_par}
             ode, cost, g, lb, ub = t.stage_call(s, vals, sx.ZERO)
             x_end = self._integrate(t, s, vals, xk, ode, sx.ZERO)
             t.pred_time = ts * (k + 1)

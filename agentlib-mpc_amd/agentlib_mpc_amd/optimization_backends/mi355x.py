@@ -171,30 +171,14 @@ class MI355XBackend(OptimizationBackend):
             raise RuntimeError("setup_optimization() must be called before solve()")
         prob = self.problem
         n = len(batch_vars)
-        src = None  # per entry: the previous call's slot of its agent (-1: cold), or None (by slot)
-        if agent_ids is not None:
-            ids = list(agent_ids)
-            if len(ids) != n or len(set(ids)) != n:
-                raise ValueError("agent_ids: one unique key per batch entry")
-            old = {k: i for i, k in enumerate(self._slot_ids or [])}
-            src = np.array([old.get(k, -1) for k in ids], np.int64)
-            self._slot_ids = ids
-        else:
-            self._slot_ids = None
+        src = self._previous_slots(n, agent_ids)
         if prob.nlp.lift is None:
             res = self._solve_resident(now, batch_vars, src)
             if self.config.save_results:
                 for i in range(n):
                     self.save_result_df(res[i], now)
             return res
-        if src is not None:
-            w_prev = None
-            if self._remembered is not None:
-                w_prev = np.full((n, self._remembered.shape[1]), np.nan)
-                hit = src >= 0
-                w_prev[hit] = self._remembered[src[hit]]
-        else:
-            w_prev = self._remembered if self._remembered is not None and self._remembered.shape[0] == n else None
+        w_prev = self._remembered_optima(n, src)
         p, lbw, ubw, w0, sampled = prob.marshal.inputs(batch_vars, now, w_prev, return_sampled_bounds=True)
         res = self.solve_arrays(p, lbw, ubw, w0, result_bounds=sampled)
         self._remembered = res.w.copy()
@@ -202,6 +186,31 @@ class MI355XBackend(OptimizationBackend):
             for i in range(n):
                 self.save_result_df(res[i], now)
         return res
+
+    def _previous_slots(self, n: int, agent_ids):
+        """Per entry the previous call's slot of its agent (-1: cold), or None when the optima are
+        kept by slot (no ``agent_ids``); remembers this call's keys."""
+        if agent_ids is None:
+            self._slot_ids = None
+            return None
+        ids = list(agent_ids)
+        if len(ids) != n or len(set(ids)) != n:
+            raise ValueError("agent_ids: one unique key per batch entry")
+        old = {k: i for i, k in enumerate(self._slot_ids or [])}
+        self._slot_ids = ids
+        return np.array([old.get(k, -1) for k in ids], np.int64)
+
+    def _remembered_optima(self, n: int, src):
+        """The host path's warm start [n, nw] (rows of NaN: cold) from the remembered optima, or
+        None."""
+        if src is None:
+            return self._remembered if self._remembered is not None and self._remembered.shape[0] == n else None
+        if self._remembered is None:
+            return None
+        w_prev = np.full((n, self._remembered.shape[1]), np.nan)
+        hit = src >= 0
+        w_prev[hit] = self._remembered[src[hit]]
+        return w_prev
 
     def _solve_resident(self, now, batch_vars, src=None):
         """Plugin batch on device-resident inputs (:mod:`.plugin_batch`): only the inputs

@@ -4,8 +4,9 @@ Restates the reference's variable-group layer:
 ``OptimizationVariable.declare`` / ``OptimizationParameter.declare``
 (`optimization_backends/casadi_/core/VariableGroup.py:39-137`, `148-223`),
 ``System`` (`core/system.py:16-74`), ``BaseSystem``
-(`casadi_/basic.py:29-101`), ``FullSystem`` (`casadi_/full.py:18-33`) and
-``CasadiADMMSystem`` (`casadi_/admm.py:23-116`).  Group declaration order is
+(`casadi_/basic.py:29-101`), ``FullSystem`` (`casadi_/full.py:18-33`),
+``CasadiADMMSystem`` (`casadi_/admm.py:23-116`) and ``CasadiMINLPSystem``
+(`casadi_/minlp.py:16-33`).  Group declaration order is
 significant: it defines the result column order (`core/discretization.py:455-481`).
 """
 
@@ -17,7 +18,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 from agentlib_mpc_amd import symbolic as sx
 from agentlib_mpc_amd.data_structures import admm_datatypes as adt
-from agentlib_mpc_amd.data_structures.mpc_datamodels import VariableReference
+from agentlib_mpc_amd.data_structures.mpc_datamodels import MINLPVariableReference, VariableReference
 from agentlib_mpc_amd.data_structures.objective import CombinedObjective, SubObjective
 from agentlib_mpc_amd.models.casadi_model import CasadiInput, CasadiModel, CasadiParameter
 
@@ -162,6 +163,18 @@ class FullSystem(BaseSystem):
         self.last_control = OptimizationParameter.declare(
             "u_prev", model.get_inputs(var_ref.controls), var_ref.controls,
             use_in_stage_function=False, assert_complete=True)
+
+
+class MINLPSystem(BaseSystem):
+    """`casadi_/minlp.py:16-33`: the base system plus the group ``w`` of the binary controls,
+    declared first (so its result columns come first).  The reference's linearity probe
+    (`minlp.py:35-60`) only sets a flag nothing on the CIA path reads; it is not restated."""
+
+    def initialize(self, model: CasadiModel, var_ref: MINLPVariableReference):
+        self.binary_controls = OptimizationVariable.declare(
+            "w", model.get_inputs(var_ref.binary_controls), var_ref.binary_controls,
+            assert_complete=True, binary=True)
+        super().initialize(model, var_ref)
 
 
 class ADMMSystem(FullSystem):

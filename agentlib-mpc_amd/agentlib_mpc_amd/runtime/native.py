@@ -96,6 +96,7 @@ EXPORTED_SYMBOLS = [
     "mpcx_admm_allreduce", "mpcx_allreduce_calls", "mpcx_rccl_unique_id", "mpcx_rccl_comm_init",
     "mpcx_rccl_comm_init_file", "mpcx_rccl_comm_destroy", "mpcx_stream_create_dedicated", "mpcx_stream_destroy",
     "mpcx_lds_bytes_per_agent", "mpcx_admm_block_expand_multi", "mpcx_stats_count_multi",
+    "mpcx_cia_round",
 ]
 MOVE_DESC = 4  # MPCX_MOVE_DESC: int64 words per descriptor of the fused row moves (C ABI v12)
 ADMM_TOTALS = 8  # MPCX_ADMM_TOTALS
@@ -119,9 +120,10 @@ def _hipcc() -> str:
 
 
 def build_library(force: bool = False) -> pathlib.Path:
-    """Compile libmpcx.so (host runtime + ADMM kernels) for gfx950, in-tree."""
+    """Compile libmpcx.so (host runtime + ADMM and rounding kernels) for gfx950, in-tree."""
     BUILD_DIR.mkdir(parents=True, exist_ok=True)
-    srcs = [CSRC / "mpcx_runtime.cpp", CSRC / "admm_kernels.hip", CSRC / "mpcx_collective.cpp"]
+    srcs = [CSRC / "mpcx_runtime.cpp", CSRC / "admm_kernels.hip", CSRC / "cia_kernels.hip",
+            CSRC / "mpcx_collective.cpp"]
     deps = srcs + [INCLUDE / "mpcx.h", CSRC / "mpcx_internal.h", CSRC / "mpcx_builds.h"]
     if LIB_PATH.exists() and not force:
         if LIB_PATH.stat().st_mtime >= max(p.stat().st_mtime for p in deps):
@@ -246,6 +248,8 @@ def load_library():
         # streams with a hardware queue of their own (C ABI v15): the fleet's class streams
         lib.mpcx_stream_create_dedicated.argtypes = [ctypes.POINTER(vp)]
         lib.mpcx_stream_destroy.argtypes = [vp]
+        # rounding of relaxed binary controls (added to C ABI v15): cia_round below
+        lib.mpcx_cia_round.argtypes = [i32, i32, i32, i32, f64] + [vp] * 10 + [vp]
         for name in EXPORTED_SYMBOLS:
             getattr(lib, name)  # raises AttributeError if a symbol is missing
         _lib = lib
@@ -291,6 +295,96 @@ def default_options() -> Options:
     opts = Options()
     load_library().mpcx_default_options(ctypes.byref(opts))
     return opts
+
+
+# ---------------------------------------------------------------------------
+# rounding of relaxed binary controls (mpcx_cia_round)
+# ---------------------------------------------------------------------------
+CIA_MAX_MODES, CIA_MAX_INTERVALS, CIA_MAX_STATES = 4, 128, 64  # MPCX_CIA_MAX_*
+CIA_OK, CIA_BAD_INPUT, CIA_BAND_OVERFLOW = 0, 1, 2  # MPCX_CIA_*
+CIA_STATUS_NAMES = {CIA_OK: "OK", CIA_BAD_INPUT: "BAD_INPUT", CIA_BAND_OVERFLOW: "BAND_OVERFLOW"}
+
+
+class CIARounding(NamedTuple):
+    """Outputs of :func:`cia_round` (device tensors, valid once the stream has run the launch)."""
+    lbw: object     # [n, nw] the fixed solve's lower bounds
+    ubw: object     # [n, nw] ... upper bounds
+    b_bin: object   # [n, n_bin * n_intervals] the binary controls, slot order (NaN: agent not OK)
+    eta: object     # [n] the integral deviation in the unit of dt (NaN: agent not OK)
+    status: object  # [n] int32 CIA_OK / CIA_BAD_INPUT / CIA_BAND_OVERFLOW
+
+
+def cia_slot_table(positions, nw: int):
+    """The slot table of ``mpcx_cia_round`` as a host int32 array [nw]: ``positions[j][i]`` is the
+    index in w of binary control j on interval i; every other entry is -1."""
+    import numpy as np
+
+    pos = np.asarray(positions, dtype=np.int64)
+    if pos.ndim != 2 or pos.size == 0:
+        raise ValueError("positions: [n_bin][n_intervals] indices into w expected")
+    if pos.min() < 0 or pos.max() >= nw or len(np.unique(pos)) != pos.size:
+        raise ValueError(f"positions must be distinct indices in [0, {nw})")
+    table = np.full(int(nw), -1, dtype=np.int32)
+    table[pos.reshape(-1)] = np.arange(pos.size, dtype=np.int32)
+    return table
+
+
+def cia_round(w, lbw, ubw, slot, n_bin: int, n_intervals: int, dt: float, out: Optional[CIARounding] = None,
+              active=None, stream=None) -> CIARounding:
+    """Round the relaxed binary controls of the solutions ``w`` [n, nw] on the device and write the
+    bounds of the fixed solve (``mpcx_cia_round``; stream-ordered, asynchronous).  ``slot``: int32
+    device tensor [nw] (:func:`cia_slot_table`); ``out``: buffers of an earlier call to reuse.
+
+    Every argument is checked here, before any HIP call: a wrong size or a host tensor would
+    otherwise be an out-of-bounds device access."""
+    import math
+
+    import torch
+
+    n_bin, N = int(n_bin), int(n_intervals)
+    if not 1 <= n_bin <= CIA_MAX_MODES:
+        raise ValueError(f"n_bin {n_bin} outside [1, {CIA_MAX_MODES}]")
+    if not 1 <= N <= CIA_MAX_INTERVALS:
+        raise ValueError(f"n_intervals {N} outside [1, {CIA_MAX_INTERVALS}]")
+    dt = float(dt)
+    if not (dt > 0.0 and math.isfinite(dt)):
+        raise ValueError(f"dt must be positive and finite, got {dt}")
+    if getattr(w, "ndim", 0) != 2:
+        raise ValueError("w must be a [n_agents, nw] tensor")
+    n, nw = int(w.shape[0]), int(w.shape[1])
+    if nw < n_bin * N:
+        raise ValueError(f"nw {nw} is smaller than n_bin * n_intervals = {n_bin * N}")
+
+    def check(name, t, shape, dtype=torch.float64):
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous {dtype} device tensor of shape {shape}, "
+                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+    for name, t in (("w", w), ("lbw", lbw), ("ubw", ubw)):
+        check(name, t, (n, nw))
+    check("slot", slot, (nw,), torch.int32)
+    if active is not None:
+        check("active", active, (n,), torch.int32)
+    if out is None:
+        out = CIARounding(torch.empty_like(lbw), torch.empty_like(ubw),
+                          torch.empty((n, n_bin * N), dtype=torch.float64, device=w.device),
+                          torch.empty((n,), dtype=torch.float64, device=w.device),
+                          torch.empty((n,), dtype=torch.int32, device=w.device))
+    else:
+        check("out.lbw", out.lbw, (n, nw))
+        check("out.ubw", out.ubw, (n, nw))
+        check("out.b_bin", out.b_bin, (n, n_bin * N))
+        check("out.eta", out.eta, (n,))
+        check("out.status", out.status, (n,), torch.int32)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    rc = load_library().mpcx_cia_round(n, nw, n_bin, N, dt, ptr(slot), ptr(w), ptr(lbw), ptr(ubw), ptr(out.lbw),
+                                       ptr(out.ubw), ptr(out.b_bin), ptr(out.eta), ptr(out.status), ptr(active),
+                                       ctypes.c_void_p(stream))
+    if rc != 0:
+        raise NativeError(f"mpcx_cia_round failed ({rc})")
+    return out
 
 
 # ---------------------------------------------------------------------------

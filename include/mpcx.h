@@ -459,6 +459,55 @@ int mpcx_rccl_comm_destroy(const char* rccl_library, void* comm);
 int mpcx_stream_create_dedicated(void** stream);
 int mpcx_stream_destroy(void* stream);
 
+/* ---- rounding of relaxed binary controls (added to C ABI v15) -------------------------------
+ * mpcx_cia_round <- the combinatorial integral approximation between the two solves of the
+ * reference's CIA backend (optimization_backends/casadi_/minlp_cia.py:99-171, pycombina's
+ * CombinaBnB with no switch or dwell limits): per agent, binary controls B[j][i] in {0, 1} with
+ * one 1 per interval (SOS1) that minimise
+ *   eta = max_{j,k} | sum_{i<=k} dt (b[j][i] - B[j][i]) |
+ * for the relaxed controls b of the solution w.  On the uniform grid of the backend the deviation
+ * after interval i depends on the choices only through the count vector c (c_j = intervals up to i
+ * given to mode j), so the optimum is a dynamic programme over c, exact and without a worst case:
+ *   S_j[i] = fp64 running sum of b[j][0..i] in ascending i;  dev(i,c) = max_j |S_j[i] - (double)c_j|
+ *   F(i,c) = max(dev(i,c), min_{j: c_j >= 1} F(i-1, c - e_j)),  F(-1, 0) = 0,  eta = dt * min_c F(N-1, c)
+ * ties: the predecessor is the smallest j, the final c the lexicographically smallest
+ * (c_0 .. c_{nc-2}).  Only compares, max, single subtractions and integer conversions: host and
+ * device agree bit for bit.  Modes: n_bin == 1 adds the row max(0, 1 - b[0][i]) (nc = 2), else
+ * nc = n_bin.  Values in (-1e-5, 0) count as 0 and values in (1, 1 + 1e-5) as 1 (minlp_cia.py:105-112).
+ * States: sum-up rounding (per interval the mode with the largest S_j[i] - c_j, the smallest j on
+ * ties) gives eta_sur in one pass; an assignment no worse keeps every c_j within eta_sur of
+ * S_j[i], so a level holds W^(nc-1) states with W = floor(2 eta_sur) + 2 counts per mode from
+ * ceil(S_j[i] - eta_sur) - 1 on (the last mode's count follows from the sum), one lane each.
+ * Limits (MPCX_ERR_ARG otherwise): n_bin <= MPCX_CIA_MAX_MODES, n_intervals <=
+ * MPCX_CIA_MAX_INTERVALS, n_bin * n_intervals <= nw; the state capacity is MPCX_CIA_MAX_STATES
+ * (for nc = 4: eta_sur < 1.5 intervals).
+ *   slot    [nw] int32 (device)  slot[k] = j * n_intervals + i where w[k] is binary control j on
+ *                                interval i, -1 elsewhere (built once per structure); every (j, i)
+ *                                must occur
+ *   w       [n_agents][nw]       the relaxed solution (mpcx_batch_solve's w_io)
+ *   lbw/ubw [n_agents][nw]       the relaxed solve's bounds
+ *   lbw_fix/ubw_fix [n_agents][nw]  out: lbw/ubw with lb = ub = B at the binary positions -- the
+ *                                bounds of the second solve
+ *   b_bin   [n_agents][n_bin * n_intervals] or NULL   out: B in slot order
+ *   eta     [n_agents]           out: eta in the unit of dt (dt applied last)
+ *   status  [n_agents] int32     out: MPCX_CIA_OK; MPCX_CIA_BAD_INPUT (a value that is not finite or
+ *                                outside [0, 1] after the clip, a (j, i) without a slot, or for
+ *                                n_bin >= 2 a column whose sum differs from 1 by more than 1e-6);
+ *                                MPCX_CIA_BAND_OVERFLOW (more states than the capacity)
+ *   active  [n_agents] int32 or NULL   agents with active[a] == 0 are skipped, outputs untouched
+ * An agent that is not MPCX_CIA_OK gets the relaxed rows as its fixed rows and eta = b_bin = NaN:
+ * its second solve repeats the relaxed problem.  The call returns 0 whatever the agents' statuses. */
+#define MPCX_CIA_MAX_MODES 4
+#define MPCX_CIA_MAX_INTERVALS 128
+#define MPCX_CIA_MAX_STATES 64
+#define MPCX_CIA_OK 0
+#define MPCX_CIA_BAD_INPUT 1
+#define MPCX_CIA_BAND_OVERFLOW 2
+int mpcx_cia_round(int32_t n_agents, int32_t nw, int32_t n_bin, int32_t n_intervals, double dt,
+                   const int32_t* slot, const double* w, const double* lbw, const double* ubw,
+                   double* lbw_fix, double* ubw_fix, double* b_bin, double* eta, int32_t* status,
+                   const int32_t* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
